@@ -9,23 +9,30 @@ What the timed region measures (truth-in-labeling):
     kernel work (probe + count over every seed row) re-executes per step.
   - --cold: the plan cache is cleared before every step, so each step pays
     parse -> Volcano plan -> distribute -> execute.
-  A 3-step cold measurement is always reported in config.cold_ms_p50.
+  With --full a 3-step cold measurement is reported in config.cold_ms_p50.
+
+A plain run sets up, warms up, times --steps steps, writes its outputs if
+--dump-outputs is given and prints the result line.  Everything else (the
+cold-latency measurement, the row-returning variant, the multi-GPU shuffle
+leg) runs only with --full.
 
 Multi GPU (torchrun, one rank per GPU): 100M triples subject-hash
 partitioned across ranks (strong scaling), executed through the
 planner-driven distributed path (PExchange ops + distributed finalize).
 The headline layout replicates the tiny department relation at load time
 and DECLARES it to the planner (its legitimate broadcast-table choice), so
-the per-step plan is exchange-free with a COUNT all-reduce.  Each run ALSO
-measures the genuine shuffle path on a second, fully-partitioned copy of
-the data: config.shuffle_ms_per_step = the same query with the 12.8M-row
+the per-step plan is exchange-free with a COUNT all-reduce.  Each --full
+run ALSO measures the genuine shuffle path on a second, fully-partitioned
+copy of the data: config.shuffle_ms_per_step = the same query with the 12.8M-row
 intermediate hash-exchanged over xGMI per step, and config.bcast_ms_per_step
 = the cost-based per-query broadcast variant.  Both counts are checked
 against the headline count.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-        --master-addr 127.0.0.1 bench.py --gpus 8 --steps 20 --warmup 5
+        --master-addr 127.0.0.1 bench.py --gpus 8 --steps 20 --warmup 5 --full
 """
 from __future__ import annotations
 
@@ -79,6 +86,15 @@ def _time_steps(fn, steps, device, use_cuda):
     return ms, lat, r
 
 
+def _dump_outputs(out_dir, count):
+    """Write what a caller of the timed path received in the last timed
+    step: the flagship query's single result row, the COUNT(*) value."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "result_count.npy"),
+            np.asarray([count], dtype=np.float64))
+
+
 def main():
     import gc
     gc.freeze()   # exclude torch's import-time object graph from gen scans
@@ -93,8 +109,16 @@ def main():
     ap.add_argument("--cold", action="store_true",
                     help="clear the plan cache every step (cold latency)")
     ap.add_argument("--no-shuffle-leg", action="store_true",
-                    help="skip the secondary shuffle measurement")
+                    help="with --full: skip the secondary shuffle measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (cold latency, "
+                         "row-returning variant, multi-GPU shuffle leg)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step returned as "
+                         "DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, world, device = D.init_from_env(args.device)
     if args.device is not None:
@@ -148,9 +172,12 @@ def main():
     qps = 1000.0 / ms_per_step
     p50 = statistics.median(lat)
 
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, c)
+
     # cold-query latency (parse -> plan -> execute), 3 steps, 1-GPU only
     cold_p50 = None
-    if world == 1 and not args.cold:
+    if args.full and world == 1 and not args.cold:
         def run_cold() -> int:
             getattr(ddb.db, "_plan_cache", {}).clear()
             return int(ddb.db.query(FLAGSHIP_QUERY)[0][0])
@@ -160,7 +187,7 @@ def main():
     # row-returning flagship variant: same 3-way join
     # shape but materializing ~n_dept/1000 x 100 result rows as strings
     rows_ms = rows_n = None
-    if world == 1:
+    if args.full and world == 1:
         city = ds.city_base + 3
         ddb.db.dictionary.str_to_id[f"http://synthetic/c{city}"] = city
         q_rows = (f"PREFIX ds: <{DS}> SELECT ?e ?sal WHERE {{ "
@@ -175,7 +202,7 @@ def main():
     # secondary measurement: the REAL shuffle path on a fully-partitioned
     # copy (no replicated relations) — BASELINE config 3's all-to-all join
     shuffle_ms = bcast_ms = None
-    if world > 1 and not args.no_shuffle_leg:
+    if args.full and world > 1 and not args.no_shuffle_leg:
         ddb2 = DistributedDatabase(rank, world, device)
         ds2 = plan_dataset(ddb2.db, total)
         s2, p2, o2 = generate_partition(ds2, rank, world, args.seed, device,
@@ -220,6 +247,7 @@ def main():
                 "result_count": c,
                 "p50_ms": p50,
                 "plan_cache": "cold" if args.cold else "warm",
+                "full": args.full,
                 "timed_region": (
                     "parse+plan+execute per step" if args.cold
                     else ("prepared distributed plan per step (local "

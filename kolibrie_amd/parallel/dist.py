@@ -23,7 +23,10 @@ def init_from_env(device_hint: Optional[str] = None) -> Tuple[int, int, torch.de
     rank = int(os.environ["RANK"])
     world = int(os.environ["WORLD_SIZE"])
     local_rank = int(os.environ.get("LOCAL_RANK", rank))
-    if torch.cuda.is_available():
+    # an explicit "cpu" hint holds on a GPU machine too (gloo ranks need no
+    # GPU each; the CPU suite runs world 2..8 on hosts with a single GPU)
+    want_cpu = device_hint is not None and torch.device(device_hint).type == "cpu"
+    if torch.cuda.is_available() and not want_cpu:
         torch.cuda.set_device(local_rank)
         dev = torch.device(f"cuda:{local_rank}")
         backend = "nccl"
