@@ -10,7 +10,8 @@ A from-scratch framework with the capabilities of StreamIntelligenceLab/Kolibrie
 - distributed join shuffle and aggregate reduction as RCCL all-to-all /
   all-reduce over xGMI (torch.distributed, backend "nccl" == RCCL on ROCm),
 - host orchestration (parsing, planning, provenance circuits) on CPU; strings
-  never touch the GPU.
+  stay on the host unless a FILTER string predicate asks for the opt-in
+  device term-text table (SparqlDatabase.term_text()).
 
 Public surface (mirrors the reference's crate layout):
   SparqlDatabase       — storage facade (ref: kolibrie/src/sparql_database.rs)

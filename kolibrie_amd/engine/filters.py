@@ -13,9 +13,15 @@ Semantics preserved exactly from the reference
   - AND / OR / NOT; arithmetic with division-by-zero => false
   - FILTER function calls support isTRIPLE (types.rs:444-455)
 
+Beyond the reference (which evaluates them to false): STRSTARTS / STRENDS /
+CONTAINS / REGEX, false on unbound and quoted-triple cells like every other
+predicate here.  They are lowered at compile time (engine/strings.py) and
+run in the K9 str_match kernel on a GPU.
+
 The vectorized evaluator below is the CPU oracle and the torch fallback; the
 HIP K5 kernel consumes the same tree serialized to postfix bytecode
-(ops/filter_bytecode.py).
+(ops/filter_bytecode.py).  A filter with a string predicate does not compile
+to bytecode: its masks are composed by the evaluator below.
 """
 from __future__ import annotations
 
@@ -28,6 +34,10 @@ from ..parsing.ast import (
 )
 from ..storage.terms import UNBOUND
 from .bindings import Bindings
+from .strings import (
+    FOLD_LOWER, FOLD_UPPER, STRING_PREDICATES, lower_predicate, oracle_mask,
+    pair_oracle_mask, string_predicate_mask,
+)
 
 
 class CompiledExpr:
@@ -41,6 +51,11 @@ class CompiledExpr:
         self._prepare(ast, db)
 
     def _prepare(self, e: Expr, db):
+        if isinstance(e, EFunc) and e.name in STRING_PREDICATES:
+            # pattern / flags literals are NOT interned: a fresh needle
+            # must not grow the dictionary (and the device text table)
+            e.str_pred = _lower_string_pred(e, db, self.prefixes)  # type: ignore[attr-defined]
+            return
         if isinstance(e, ELit):
             if e.is_number:
                 e.num_value = float(e.value)  # type: ignore[attr-defined]
@@ -214,6 +229,8 @@ def _eval_bool(e: Expr, b: Bindings, db) -> torch.Tensor:
             if not b.has(v):
                 return torch.zeros(b.n, dtype=torch.bool, device=dev)
             return b.col(v) != UNBOUND
+        if e.name in STRING_PREDICATES:
+            return _eval_string_pred(e, b, db)
         # other functions are false in FILTER context (ref types.rs:444-455)
         return torch.zeros(b.n, dtype=torch.bool, device=dev)
     if isinstance(e, EVar):
@@ -224,12 +241,116 @@ def _eval_bool(e: Expr, b: Bindings, db) -> torch.Tensor:
     raise ValueError(f"cannot evaluate {e} as boolean")
 
 
+# -------------------------------------------------------- string predicates --
+class _StringPred:
+    """A lowered STRSTARTS / STRENDS / CONTAINS / REGEX call.
+
+    subject: ("var", name) or ("const", text); transforms: LCASE/UCASE folds
+    of the subject, innermost first.  With a literal pattern `plan` is the
+    lowered predicate (engine/strings.py); with a variable pattern
+    `pattern_var` names it and (func, flags) are kept for the host path."""
+
+    __slots__ = ("func", "subject", "transforms", "plan", "pattern_var",
+                 "flags")
+
+
+def _literal_text(e: ELit, db, prefixes) -> str:
+    if e.is_number:
+        return e.value
+    return db.resolve_lexical(e.value, prefixes)
+
+
+def _lower_string_pred(e: EFunc, db, prefixes) -> "_StringPred":
+    n_args = len(e.args)
+    if not (n_args == 2 or (e.name == "REGEX" and n_args == 3)):
+        raise ValueError(f"{e.name} takes 2 arguments"
+                         + (" or 3" if e.name == "REGEX" else "")
+                         + f", got {n_args}")
+    sp = _StringPred()
+    sp.func = e.name
+    # first argument: ?v | literal, under any nesting of STR / LCASE / UCASE
+    folds: List[int] = []
+    subj = e.args[0]
+    while isinstance(subj, EFunc) and subj.name in ("STR", "LCASE", "UCASE") \
+            and len(subj.args) == 1:
+        if subj.name != "STR":
+            folds.append(FOLD_LOWER if subj.name == "LCASE" else FOLD_UPPER)
+        subj = subj.args[0]
+    folds.reverse()                       # innermost first
+    # folding twice the same way is folding once
+    sp.transforms = tuple(f for i, f in enumerate(folds)
+                          if i == 0 or folds[i - 1] != f)
+    if isinstance(subj, EVar):
+        sp.subject = ("var", subj.name)
+    elif isinstance(subj, ELit):
+        sp.subject = ("const", _literal_text(subj, db, prefixes))
+    else:
+        raise ValueError(f"{e.name}: first argument must be a variable or "
+                         f"literal, optionally inside STR/LCASE/UCASE")
+    sp.flags = ""
+    if n_args == 3:
+        if not isinstance(e.args[2], ELit):
+            raise ValueError("REGEX: flags must be a string literal")
+        sp.flags = _literal_text(e.args[2], db, prefixes)
+    pat = e.args[1]
+    sp.plan = None
+    sp.pattern_var = None
+    if isinstance(pat, ELit):
+        sp.plan = lower_predicate(e.name, _literal_text(pat, db, prefixes),
+                                  sp.transforms, sp.flags)
+    elif isinstance(pat, EVar):
+        sp.pattern_var = pat.name
+        lower_predicate(e.name, "", sp.transforms, sp.flags)  # checks flags
+    else:
+        raise ValueError(f"{e.name}: second argument must be a literal or "
+                         f"a variable")
+    return sp
+
+
+def _eval_string_pred(e: EFunc, b: Bindings, db) -> torch.Tensor:
+    sp = getattr(e, "str_pred", None)
+    if sp is None:   # AST evaluated without CompiledExpr preparation
+        sp = e.str_pred = _lower_string_pred(e, db, {})  # type: ignore[attr-defined]
+    dev = b.device
+    kind, subj = sp.subject
+    if sp.pattern_var is None:
+        if kind == "const":
+            hit = sp.plan.test(subj)
+            return torch.full((b.n,), hit, dtype=torch.bool, device=dev)
+        if not b.has(subj):
+            return torch.zeros(b.n, dtype=torch.bool, device=dev)
+        return string_predicate_mask(sp.func, b.col(subj), sp.plan.needle,
+                                     sp.transforms, sp.flags, db,
+                                     plan=sp.plan)
+    # variable pattern: host path over distinct (term, pattern) pairs
+    if not b.has(sp.pattern_var) or (kind == "var" and not b.has(subj)):
+        return torch.zeros(b.n, dtype=torch.bool, device=dev)
+    plans: Dict[str, object] = {}
+
+    def test_with(pattern: str, term: str) -> bool:
+        p = plans.get(pattern)
+        if p is None:
+            try:
+                p = lower_predicate(sp.func, pattern, sp.transforms, sp.flags)
+            except ValueError:
+                p = False        # an invalid pattern is an error: row false
+            plans[pattern] = p
+        return p is not False and p.test(term)
+
+    pat_ids = b.col(sp.pattern_var)
+    if kind == "const":
+        return oracle_mask(pat_ids, lambda p: test_with(p, subj), db)
+    return pair_oracle_mask(b.col(subj), pat_ids,
+                            lambda t, p: test_with(p, t), db)
+
+
 # --------------------------------------------------------------------- BIND --
 class CompiledBind:
     """BIND(expr AS ?v) evaluator (ref engine.rs:527-677: CONCAT / UDF /
     TRIPLE / SUBJECT / PREDICATE / OBJECT / isTRIPLE; we add arithmetic).
 
-    String-producing functions run on host (strings never touch the GPU);
+    String-producing functions run on host (only FILTER string predicates
+    read term text on the GPU);
     TRIPLE/SUBJECT/... use the quoted-triple store.
     """
 

@@ -10,6 +10,9 @@
 //                     and shared/src/join_algorithm.rs:64-265)
 //   K5 filter      — postfix-bytecode predicate over id columns + the f64
 //                    value column (replaces types.rs:373 evaluate_with_ids).
+//   K9 str_match   — STRSTARTS / STRENDS / CONTAINS / literal REGEX over the
+//                    device term-text table (the reference evaluates these
+//                    to false).
 //
 // Design notes (per CDNA4 guide): wave64, 256-thread blocks, grid-stride
 // loops capped so the 256-CU chip is saturated without oversubscription;
@@ -554,6 +557,239 @@ __global__ void filter_eval(FilterProg prog, BindCols cols,
       }
     }
     out[row] = sb > 0 ? bools[sb-1] : false;
+  }
+}
+
+// ------------------------------------------------------- K9 str_match kernels
+// FILTER string predicates over the device term-text table: row i tests the
+// UTF-8 of term ids[i] (bytes[offsets[id] .. offsets[id+1])) against one
+// constant needle.  Output per row: 0 = no match, 1 = match, 2 = undecided
+// (case folding met a non-ASCII byte before the row was decided; the host
+// resolves those with Python's Unicode rules).
+enum StrMode : int32_t { SM_STARTS = 0, SM_ENDS, SM_CONTAINS, SM_EQUALS };
+enum StrFold : int32_t { SF_NONE = 0, SF_LOWER, SF_UPPER };
+
+constexpr int kStrMaxNeedle = 255;
+constexpr int kStrNeedleQ = 32;        // needle staged as 32 qwords of LDS
+// CONTAINS rows whose term is longer than this leave the one-lane-per-row
+// kernel for the one-wave-per-term kernel.  Measured on an MI355X over
+// 10M rows (profiles/strfilter_measurements.md): a full scan (needle that
+// never matches) is flat within 2-7% for 128..512 B and degrades on either
+// side (lower: atomics + second launch for rows one lane handles well;
+// higher: one lane scans while 63 idle); with an early match the larger
+// value wins, so 512.
+constexpr int64_t kStrLongThreshold = 512;
+constexpr int kStrLongGrid = 1024;     // fixed grid of the long-term launch
+constexpr uint64_t kHiBits = 0x8080808080808080ull;
+
+// Aligned 8-byte load of qword q of the text blob.  `cap` is the blob's byte
+// count: a trailing partial qword is assembled bytewise and anything past
+// it reads as zero, so no lane ever touches memory outside [0, cap).
+__device__ __forceinline__ uint64_t str_ld_q(const uint8_t* __restrict__ bytes,
+                                             int64_t q, int64_t cap) {
+  if (q < 0) return 0;
+  if ((q + 1) * 8 <= cap)
+    return reinterpret_cast<const uint64_t*>(bytes)[q];
+  uint64_t v = 0;
+  for (int64_t b = q * 8; b < cap; ++b)
+    v |= static_cast<uint64_t>(bytes[b]) << (8 * (b - q * 8));
+  return v;
+}
+
+// 8 bytes starting at arbitrary byte position p, from two aligned loads.
+__device__ __forceinline__ uint64_t str_window(const uint8_t* __restrict__ bytes,
+                                               int64_t p, int64_t cap) {
+  int64_t q = p >> 3;
+  int sh = static_cast<int>(p & 7) * 8;
+  uint64_t lo = str_ld_q(bytes, q, cap);
+  if (sh == 0) return lo;
+  uint64_t hi = str_ld_q(bytes, q + 1, cap);
+  return (lo >> sh) | (hi << (64 - sh));
+}
+
+// mask of the low k bytes (k >= 8 -> all)
+__device__ __forceinline__ uint64_t str_byte_mask(int64_t k) {
+  return k >= 8 ? ~0ull : ((1ull << (8 * k)) - 1ull);
+}
+
+// SWAR ASCII case fold of 8 bytes; bytes >= 0x80 pass through unchanged.
+__device__ __forceinline__ uint64_t str_fold_q(uint64_t x, int32_t fold) {
+  if (fold == SF_NONE) return x;
+  uint64_t x7 = x & 0x7f7f7f7f7f7f7f7full;
+  uint64_t ge_lo, gt_hi;
+  if (fold == SF_LOWER) {            // 'A'(0x41) .. 'Z'(0x5a)
+    ge_lo = x7 + 0x3f3f3f3f3f3f3f3full;
+    gt_hi = x7 + 0x2525252525252525ull;
+  } else {                           // 'a'(0x61) .. 'z'(0x7a)
+    ge_lo = x7 + 0x1f1f1f1f1f1f1f1full;
+    gt_hi = x7 + 0x0505050505050505ull;
+  }
+  uint64_t letter = ge_lo & ~gt_hi & ~x & kHiBits;
+  return x ^ (letter >> 2);          // flip bit 0x20 of each letter
+}
+
+// any byte >= 0x80 in [start, end)?
+__device__ __forceinline__ bool str_has_high(const uint8_t* __restrict__ bytes,
+                                             int64_t start, int64_t end,
+                                             int64_t cap) {
+  for (int64_t p = start; p < end; p += 8)
+    if (str_window(bytes, p, cap) & str_byte_mask(end - p) & kHiBits)
+      return true;
+  return false;
+}
+
+// needle[0..m) against the (folded) bytes at p: 1 match, 0 mismatch, 2 met a
+// non-ASCII byte under folding before any mismatch.  Chunks before a
+// mismatch are pure ASCII, so for a window anchored at its FRONT (or an
+// interior CONTAINS candidate, where a 0 only means "not here") a 0 holds
+// under Unicode folding as well.  A back-anchored caller (ENDS) must rule
+// out non-ASCII bytes in the whole window first.
+__device__ __forceinline__ int str_cmp_at(const uint8_t* __restrict__ bytes,
+                                          int64_t p, int64_t cap,
+                                          const uint64_t* needle_q, int m,
+                                          int32_t fold) {
+  for (int k = 0; k < m; k += 8) {
+    uint64_t t = str_window(bytes, p + k, cap);
+    uint64_t mask = str_byte_mask(m - k);
+    if (fold != SF_NONE) {
+      if (t & mask & kHiBits) return 2;
+      t = str_fold_q(t, fold);
+    }
+    if ((t ^ needle_q[k >> 3]) & mask) return 0;
+  }
+  return 1;
+}
+
+// Short-term kernel: one lane per row.  CONTAINS rows with a long term are
+// appended to the overflow list instead of being scanned here.
+__global__ void str_match_rows(const int32_t* __restrict__ ids, int64_t n,
+                               const uint8_t* __restrict__ bytes, int64_t cap,
+                               const int64_t* __restrict__ offsets, int64_t V,
+                               const uint64_t* __restrict__ needle, int m,
+                               int32_t mode, int32_t fold,
+                               uint8_t* __restrict__ out,
+                               int32_t* __restrict__ ovf_count,
+                               int32_t* __restrict__ ovf_rows) {
+  __shared__ uint64_t s_needle[kStrNeedleQ];
+  if (threadIdx.x < kStrNeedleQ) s_needle[threadIdx.x] = needle[threadIdx.x];
+  __syncthreads();
+  for (int64_t row = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; row < n;
+       row += (int64_t)gridDim.x * blockDim.x) {
+    int32_t id = ids[row];
+    uint8_t r = 0;
+    if (id >= 0 && id < V) {       // unbound, quoted and unknown ids: 0
+      int64_t start = offsets[id];
+      int64_t end = offsets[id + 1];
+      int64_t len = end - start;
+      if (start < 0 || len < 0 || end > cap) {
+        r = 0;                     // corrupt table: never read it
+      } else if (m == 0) {
+        r = (mode == SM_EQUALS) ? (len == 0) : 1;
+      } else if (len < m) {
+        // a folded non-ASCII term may grow (UCASE("ß") = "SS")
+        r = (fold != SF_NONE && str_has_high(bytes, start, end, cap)) ? 2 : 0;
+      } else if (mode == SM_EQUALS && len != m) {
+        // a character of <= 4 bytes folds to >= 1 character, so only terms
+        // up to 4*m bytes can fold down to m characters
+        r = (fold != SF_NONE && len <= 4 * (int64_t)m
+             && str_has_high(bytes, start, end, cap)) ? 2 : 0;
+      } else if (mode != SM_CONTAINS) {
+        int64_t w0 = (mode == SM_ENDS) ? end - m : start;
+        // STARTS / EQUALS are front-aligned: the ASCII chunks before a
+        // mismatch fold 1:1, so str_cmp_at's early 0 is final.  ENDS is
+        // back-aligned: a character later in the window whose fold changes
+        // its byte length ("ı" -> "I", U+212A -> "k") shifts the folded
+        // suffix against the raw window, so no chunk may answer 0 before
+        // the WHOLE window is known to be ASCII.
+        if (mode == SM_ENDS && fold != SF_NONE
+            && str_has_high(bytes, w0, end, cap))
+          r = 2;
+        else
+          r = static_cast<uint8_t>(
+              str_cmp_at(bytes, w0, cap, s_needle, m, fold));
+      } else if (len > kStrLongThreshold) {
+        int32_t slot = atomicAdd(ovf_count, 1);
+        ovf_rows[slot] = static_cast<int32_t>(row);   // slot < n by count
+        r = 0;
+      } else {
+        // slide over every start position; the two aligned qwords under
+        // the window are folded once on load and reused for 8 positions
+        int64_t last = end - m;
+        int64_t q = start >> 3;
+        uint64_t lo = str_fold_q(str_ld_q(bytes, q, cap), fold);
+        uint64_t hi = str_fold_q(str_ld_q(bytes, q + 1, cap), fold);
+        uint64_t n0 = s_needle[0];
+        uint64_t mask0 = str_byte_mask(m);
+        bool found = false;
+        for (int64_t p = start; p <= last; ++p) {
+          int sh = static_cast<int>(p & 7) * 8;
+          if (sh == 0 && p != start) {
+            ++q;
+            lo = hi;
+            hi = str_fold_q(str_ld_q(bytes, q + 1, cap), fold);
+          }
+          uint64_t t = sh ? ((lo >> sh) | (hi << (64 - sh))) : lo;
+          if (((t ^ n0) & mask0) == 0) {
+            if (m <= 8 || str_cmp_at(bytes, p + 8, cap, s_needle + 1, m - 8,
+                                     fold) == 1) {
+              found = true;
+              break;
+            }
+          }
+        }
+        // an all-ASCII match is final; a miss is final only if no byte of
+        // the term could fold differently
+        if (found) r = 1;
+        else r = (fold != SF_NONE && str_has_high(bytes, start, end, cap))
+                     ? 2 : 0;
+      }
+    }
+    out[row] = r;
+  }
+}
+
+// Long-term kernel: one wave per overflow row, lanes take consecutive start
+// positions, a ballot combines them.  Fixed grid; the row count is read
+// from device memory so the host never waits between the two launches.
+__global__ void str_match_long(const int32_t* __restrict__ ids,
+                               const uint8_t* __restrict__ bytes, int64_t cap,
+                               const int64_t* __restrict__ offsets,
+                               const uint64_t* __restrict__ needle, int m,
+                               int32_t fold, uint8_t* __restrict__ out,
+                               const int32_t* __restrict__ ovf_count,
+                               const int32_t* __restrict__ ovf_rows) {
+  __shared__ uint64_t s_needle[kStrNeedleQ];
+  if (threadIdx.x < kStrNeedleQ) s_needle[threadIdx.x] = needle[threadIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int64_t count = *ovf_count;
+  for (int64_t w = wave; w < count; w += n_waves) {   // wave-uniform
+    int32_t row = ovf_rows[w];
+    int32_t id = ids[row];
+    int64_t start = offsets[id];
+    int64_t end = offsets[id + 1];
+    int64_t last = end - m;
+    bool found = false;
+    for (int64_t base = start; base <= last; base += 64) {
+      int64_t p = base + lane;
+      bool hit = p <= last
+                 && str_cmp_at(bytes, p, cap, s_needle, m, fold) == 1;
+      if (__ballot(hit) != 0ull) { found = true; break; }
+    }
+    uint8_t r = 1;
+    if (!found) {
+      r = 0;
+      if (fold != SF_NONE) {
+        bool high = false;
+        for (int64_t p = start + (int64_t)lane * 8; p < end; p += 512)
+          high |= (str_window(bytes, p, cap) & str_byte_mask(end - p)
+                   & kHiBits) != 0;
+        if (__ballot(high) != 0ull) r = 2;
+      }
+    }
+    if (lane == 0) out[row] = r;
   }
 }
 
@@ -1652,6 +1888,65 @@ at::Tensor filter_bytecode(at::Tensor ops, at::Tensor args, at::Tensor consts,
   return out;
 }
 
+// K9 string predicate -> (uint8 mask of 0/1/2, int32[1] overflow count).
+// `needle` is the pattern zero-padded to 256 bytes on the device, `m` its
+// real length.  With fold != NONE the caller passes an ASCII needle already
+// in the folded case.  The overflow count stays on the device (no sync); it
+// is the number of rows the long-term kernel handled.
+py::tuple str_match(at::Tensor ids, at::Tensor bytes, at::Tensor offsets,
+                    int64_t V, at::Tensor needle, int64_t m, int64_t mode,
+                    int64_t fold) {
+  TORCH_CHECK(ids.is_cuda() && ids.dtype() == at::kInt && ids.dim() == 1
+              && ids.is_contiguous(), "str_match: ids must be int32 on device");
+  TORCH_CHECK(bytes.is_cuda() && bytes.dtype() == at::kByte
+              && bytes.is_contiguous(), "str_match: bytes must be uint8");
+  TORCH_CHECK(offsets.is_cuda() && offsets.dtype() == at::kLong
+              && offsets.is_contiguous(), "str_match: offsets must be int64");
+  TORCH_CHECK(needle.is_cuda() && needle.dtype() == at::kByte
+              && needle.is_contiguous()
+              && needle.numel() == kStrNeedleQ * 8,
+              "str_match: needle must be 256 padded bytes on device");
+  TORCH_CHECK(m >= 0 && m <= kStrMaxNeedle, "str_match: needle too long");
+  TORCH_CHECK(mode >= SM_STARTS && mode <= SM_EQUALS, "str_match: bad mode");
+  TORCH_CHECK(fold >= SF_NONE && fold <= SF_UPPER, "str_match: bad fold");
+  TORCH_CHECK(V >= 0 && offsets.numel() >= V + 1,
+              "str_match: offsets shorter than V + 1");
+  const int64_t n = ids.numel();
+  TORCH_CHECK(n < (int64_t(1) << 31), "str_match: too many rows");
+  auto out = at::empty({n}, ids.options().dtype(at::kByte));
+  auto ovf_count = at::zeros({1}, ids.options());
+  if (n == 0) return py::make_tuple(out, ovf_count);
+  // qword loads need an 8-aligned base (always true of a fresh allocation;
+  // a view at an odd byte offset is refused rather than misread)
+  const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(bp) % 8 == 0
+              && reinterpret_cast<uintptr_t>(needle.data_ptr<uint8_t>()) % 8 == 0,
+              "str_match: byte buffers must be 8-byte aligned");
+  const bool may_overflow = (mode == SM_CONTAINS && m > 0);
+  auto ovf_rows = at::empty({may_overflow ? n : 1}, ids.options());
+  const uint64_t* nq =
+      reinterpret_cast<const uint64_t*>(needle.data_ptr<uint8_t>());
+  hipLaunchKernelGGL(str_match_rows, dim3(grid_for(n)), dim3(kBlock), 0,
+                     cur_stream(), ids.data_ptr<int32_t>(), n, bp,
+                     bytes.numel(), offsets.data_ptr<int64_t>(), V, nq,
+                     static_cast<int>(m), static_cast<int32_t>(mode),
+                     static_cast<int32_t>(fold), out.data_ptr<uint8_t>(),
+                     ovf_count.data_ptr<int32_t>(),
+                     ovf_rows.data_ptr<int32_t>());
+  HIP_OK(hipGetLastError());
+  if (may_overflow) {
+    hipLaunchKernelGGL(str_match_long, dim3(kStrLongGrid), dim3(kBlock), 0,
+                       cur_stream(), ids.data_ptr<int32_t>(), bp,
+                       bytes.numel(), offsets.data_ptr<int64_t>(), nq,
+                       static_cast<int>(m), static_cast<int32_t>(fold),
+                       out.data_ptr<uint8_t>(),
+                       ovf_count.data_ptr<int32_t>(),
+                       ovf_rows.data_ptr<int32_t>());
+    HIP_OK(hipGetLastError());
+  }
+  return py::make_tuple(out, ovf_count);
+}
+
 // ------------------------------------------------- host bulk N-Triples parse
 // Native replacement for the reference's crossbeam parse pipeline
 // (sparql_database.rs:636-795): one pass tokenizes lines, interns terms in
@@ -2479,6 +2774,33 @@ py::list vocab_export_strings(int64_t h, int64_t start, int64_t count) {
     out.append(py::reinterpret_steal<py::object>(u));
   }
   return out;
+}
+
+// annex terms [start, start+count) packed for the device term-text table:
+// (uint8 blob of their concatenated UTF-8, int64 byte length per term),
+// copied straight from the by_id views — no Python str objects.  `start`
+// is annex-relative (id - base); the range is clamped to the annex.
+py::tuple vocab_pack_bytes(int64_t h, int64_t start, int64_t count) {
+  Vocab& v = *g_vocabs.at(h);
+  int64_t n = static_cast<int64_t>(v.by_id.size());
+  int64_t lo = std::min(std::max<int64_t>(start, 0), n);
+  int64_t hi = std::min(lo + std::max<int64_t>(count, 0), n);
+  auto lens = at::empty({hi - lo}, at::kLong);
+  int64_t* lp = lens.data_ptr<int64_t>();
+  int64_t total = 0;
+  for (int64_t k = lo; k < hi; ++k) {
+    lp[k - lo] = static_cast<int64_t>(v.by_id[k].size());
+    total += lp[k - lo];
+  }
+  auto blob = at::empty({total}, at::kByte);
+  uint8_t* bp = total ? blob.data_ptr<uint8_t>() : nullptr;
+  int64_t at_byte = 0;
+  for (int64_t k = lo; k < hi; ++k) {
+    std::string_view s = v.by_id[k];
+    if (!s.empty()) memcpy(bp + at_byte, s.data(), s.size());
+    at_byte += static_cast<int64_t>(s.size());
+  }
+  return py::make_tuple(blob, lens);
 }
 
 // file -> parse -> intern DIRECTLY into the vocab annex (no Python-object
@@ -3542,4 +3864,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K2 count-only hash join -> per-left-row match counts");
   m.def("filter_bytecode", &filter_bytecode,
         "K5 filter bytecode evaluation -> bool mask");
+  m.def("str_match", &str_match,
+        "K9 string predicate over the term-text table -> "
+        "(uint8 mask 0/1/2, device overflow-row count)");
+  m.def("str_long_threshold",
+        []() { return static_cast<int64_t>(kStrLongThreshold); },
+        "term length above which CONTAINS rows take the long-term kernel");
+  m.def("vocab_pack_bytes", &vocab_pack_bytes,
+        "annex terms packed as (uint8 blob, int64 lengths)");
 }

@@ -22,6 +22,12 @@ _CMP_VAL = {"<": OP_LT, ">": OP_GT, "<=": OP_LE, ">=": OP_GE,
             "=": OP_EQ_VAL, "!=": OP_NE_VAL}
 
 
+# keep equal to engine.strings.STRING_PREDICATES (not imported: this module
+# loads lazily from engine.filters and must not import the engine package at
+# module level); tests/test_string_filters.py asserts the two agree
+_STRING_PREDICATES = ("STRSTARTS", "STRENDS", "CONTAINS", "REGEX")
+
+
 class BytecodeError(ValueError):
     pass
 
@@ -140,6 +146,10 @@ class _Compiler:
                     return
                 self.emit(OP_BOUND, self.var_cols[e.args[0].name])
                 return
+            if e.name in _STRING_PREDICATES:
+                # evaluated by the str_match kernel, not by K5: the caller
+                # composes the masks (engine/filters.py _eval_bool)
+                raise BytecodeError(f"{e.name} is not a bytecode op")
             # other functions are false in FILTER context
             self.emit(OP_PUSH_FALSE)
             return

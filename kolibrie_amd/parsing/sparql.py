@@ -672,6 +672,7 @@ class Parser:
                 return EFunc(name.upper() if name.upper() in (
                     "CONCAT", "TRIPLE", "SUBJECT", "PREDICATE", "OBJECT",
                     "ISTRIPLE", "STR", "UCASE", "LCASE",
+                    "STRSTARTS", "STRENDS", "CONTAINS", "REGEX",
                 ) else name, args)
             self.next()
             return ELit(t.text)

@@ -129,6 +129,74 @@ def split_quoted_triple_content(inner: str) -> Tuple[str, str, str]:
     return parts[0], parts[1], parts[2]
 
 
+class _TermText:
+    """Append-only device copy of the dictionary's term text (see
+    SparqlDatabase.term_text).  `bytes_buf` / `offsets_buf` are capacity
+    buffers; the first `n_bytes` bytes / `n_terms + 1` offsets are live.
+    Growing past capacity allocates max(2 * capacity, needed) and copies
+    the live prefix device-to-device; otherwise the tail is uploaded in
+    place."""
+
+    __slots__ = ("dictionary", "device", "bytes_buf", "offsets_buf",
+                 "n_terms", "n_bytes")
+
+    MIN_BYTES = 4096
+    MIN_TERMS = 512
+
+    def __init__(self, dictionary, device):
+        self.dictionary = dictionary
+        self.device = device
+        self.bytes_buf = torch.empty(0, dtype=torch.uint8, device=device)
+        self.offsets_buf = torch.zeros(1, dtype=torch.int64, device=device)
+        self.n_terms = 0
+        self.n_bytes = 0
+
+    @staticmethod
+    def _grown(buf: torch.Tensor, live: int, need: int, floor: int):
+        cap = buf.numel()
+        if need <= cap:
+            return buf
+        new = torch.empty(max(2 * cap, need, floor), dtype=buf.dtype,
+                          device=buf.device)
+        new[:live].copy_(buf[:live])
+        return new
+
+    def append(self, blob, lens):
+        """blob: uint8 numpy bytes of the new terms; lens: int64 numpy byte
+        length of each."""
+        import numpy as np
+        k = int(lens.shape[0])
+        nb = int(blob.shape[0])
+        self.bytes_buf = self._grown(self.bytes_buf, self.n_bytes,
+                                     self.n_bytes + nb, self.MIN_BYTES)
+        self.offsets_buf = self._grown(self.offsets_buf, self.n_terms + 1,
+                                       self.n_terms + k + 1, self.MIN_TERMS)
+        if nb:
+            self.bytes_buf[self.n_bytes:self.n_bytes + nb].copy_(
+                torch.from_numpy(np.ascontiguousarray(blob).copy()))
+        if k:
+            ends = self.n_bytes + np.cumsum(lens, dtype=np.int64)
+            self.offsets_buf[self.n_terms + 1:self.n_terms + 1 + k].copy_(
+                torch.from_numpy(ends))
+        self.n_terms += k
+        self.n_bytes += nb
+
+
+def device_term_text(db) -> Tuple[torch.Tensor, torch.Tensor]:
+    """SparqlDatabase.term_text for any object with `dictionary` and
+    `device` (the reasoner's filter-only database stand-in included); the
+    table is cached on the object as `_term_text_cache`."""
+    d = db.dictionary
+    n = len(d)
+    tt = getattr(db, "_term_text_cache", None)
+    if tt is None or tt.dictionary is not d or tt.n_terms > n:
+        tt = db._term_text_cache = _TermText(d, db.device)
+    if tt.n_terms < n:
+        blob, lens = d.pack_text(tt.n_terms, n)
+        tt.append(blob, lens)
+    return tt.bytes_buf[:tt.n_bytes], tt.offsets_buf[:tt.n_terms + 1]
+
+
 class SparqlDatabase:
     """The database facade.  `device` selects where columns live
     ("cpu" for host plumbing/tests, "cuda:N" for an MI355X)."""
@@ -154,6 +222,9 @@ class SparqlDatabase:
         self._stats_version = -1
         self._value_col_cache: Optional[torch.Tensor] = None
         self._value_col_len = 0
+        # device term-text table; stays None until the first FILTER string
+        # predicate asks for it (term_text())
+        self._term_text_cache: Optional[_TermText] = None
 
     # ------------------------------------------------------------------ terms
     def resolve_prefixed(self, name: str, prefixes: Optional[Dict[str, str]] = None) -> str:
@@ -417,6 +488,18 @@ class SparqlDatabase:
             self._value_col_cache = torch.from_numpy(arr).to(self.device)
             self._value_col_len = n
         return self._value_col_cache
+
+    # -------------------------------------------------------------- term text
+    def term_text(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Device-resident UTF-8 of every plain term: `(bytes_u8,
+        offsets_i64)` with term i at `bytes[offsets[i]:offsets[i+1]]`.
+
+        Built on the first FILTER string predicate and not before.  The
+        dictionary is append-only, so when it has grown only the new tail
+        is packed and uploaded, into buffers whose capacity doubles; the
+        bytes already on the device are never re-packed.  Costs the
+        vocabulary's UTF-8 size + 8 bytes per term of device memory."""
+        return device_term_text(self)
 
     # --------------------------------------------------------- quoted columns
     def quoted_columns(self):

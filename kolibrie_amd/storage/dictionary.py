@@ -1,11 +1,20 @@
 """Host-side bidirectional string <-> u32 dictionary.
 
-Strings never touch the GPU: kernels see only int32 IDs.  Alongside the
-string table we maintain a *numeric value column* (float64 per ID, parsed at
-encode time, non-numeric => 0.0) that is uploaded to the device so FILTER
-ordering comparisons and aggregates never decode strings (the reference
-decodes and `parse::<f64>().unwrap_or(0.0)` per row —
-streamertail_optimizer/execution/types.rs:349-359; we pre-parse once).
+Joins, scans, numeric FILTERs and aggregates never see strings: kernels work
+on int32 IDs.  Alongside the string table we maintain a *numeric value
+column* (float64 per ID, parsed at encode time, non-numeric => 0.0) that is
+uploaded to the device so FILTER ordering comparisons and aggregates never
+decode strings (the reference decodes and `parse::<f64>().unwrap_or(0.0)`
+per row — streamertail_optimizer/execution/types.rs:349-359; we pre-parse
+once).
+
+The one exception is opt-in: the first FILTER string predicate (STRSTARTS /
+STRENDS / CONTAINS / REGEX) makes `SparqlDatabase.term_text()` upload a
+packed UTF-8 copy of every term (`pack_text` below) for the `str_match`
+kernel.  It costs the vocabulary's UTF-8 size plus 8 bytes per term of
+device memory (up to 2x while a doubling reallocation is in flight) and is
+extended append-only; a database that never runs a string predicate never
+builds it.
 
 RDF-star quoted triples are interned with bit 31 set
 (ref: shared/src/quoted_triple_store.rs:17-80) and recurse on encode/decode
@@ -183,6 +192,48 @@ class Dictionary:
             return pre
         tail = self.annex[0].vocab_values(self.annex[1]).numpy()
         return np.concatenate([pre, tail]) if tail.size else pre
+
+    def pack_text(self, start: int, end: int):
+        """UTF-8 of terms [start, end) over the WHOLE id space, packed for
+        the device term-text table: (uint8 numpy blob, int64 numpy byte
+        length per term).  The Python prefix is one join + one encode (byte
+        lengths come from a vectorized per-character width pass, not a
+        per-term encode); the annex part is copied natively."""
+        import numpy as np
+        p0 = len(self.id_to_str)
+        blobs = []
+        lens = []
+        if start < min(end, p0):
+            tail = self.id_to_str[start:min(end, p0)]
+            joined = "".join(tail)
+            blob = joined.encode("utf-8", "surrogatepass")
+            nchars = np.fromiter(map(len, tail), dtype=np.int64,
+                                 count=len(tail))
+            if len(blob) == len(joined):          # pure ASCII
+                nbytes = nchars
+            else:
+                cp = np.frombuffer(
+                    joined.encode("utf-32-le", "surrogatepass"),
+                    dtype=np.uint32)
+                width = (1 + (cp >= 0x80) + (cp >= 0x800)
+                         + (cp >= 0x10000)).astype(np.int64)
+                csum = np.concatenate(
+                    [np.zeros(1, dtype=np.int64), np.cumsum(width)])
+                ends = np.cumsum(nchars)
+                nbytes = csum[ends] - csum[ends - nchars]
+            blobs.append(np.frombuffer(blob, dtype=np.uint8))
+            lens.append(nbytes)
+        if self.annex is not None and end > p0:
+            mod, h = self.annex
+            a0 = max(start, p0) - p0
+            b, l = mod.vocab_pack_bytes(h, a0, end - p0 - a0)
+            blobs.append(b.numpy())
+            lens.append(l.numpy())
+        if not blobs:
+            return (np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.int64))
+        if len(blobs) == 1:
+            return blobs[0], lens[0]
+        return np.concatenate(blobs), np.concatenate(lens)
 
     def iter_strings(self):
         """Iterate every interned string in id order (checkpoint/merge);
