@@ -1082,9 +1082,16 @@ at::Tensor build_count_table(at::Tensor packed_entries) {
   return table;
 }
 
+// The chain kernel's own tile: each thread owns kChainSeeds CONSECUTIVE
+// seeds (one dwordx4 per seed column), a block owns kChainTile of them.
+// Separate from kTile, which the merge-path probes above share.
+constexpr int kChainSeeds = 4;
+constexpr int kChainTile = kChainSeeds * kBlock;
+
 // per-(tile, src0-hop) windows: the seed region is subject-sorted, so the
-// B component is monotone — each 256-seed tile's src-0 hop keys fall in a
-// narrow window of that hop's region (merge-path; computed in parallel).
+// B component is monotone — each kChainTile-seed tile's src-0 hop keys fall
+// in a narrow window of that hop's region (merge-path; computed in
+// parallel).
 __global__ void chain_tile_bounds(const int32_t* __restrict__ seed_b,
                                   int64_t m, int64_t n_tiles, ChainHops hops,
                                   int64_t* __restrict__ win,  // [n_tiles][k][2]
@@ -1094,9 +1101,9 @@ __global__ void chain_tile_bounds(const int32_t* __restrict__ seed_b,
     *total_zero = 0ULL;  // saves the serve path a hipMemsetAsync enqueue
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n_tiles;
        t += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t first_b = static_cast<uint32_t>(seed_b[t * kTile]);
+    uint32_t first_b = static_cast<uint32_t>(seed_b[t * kChainTile]);
     uint32_t last_b =
-        static_cast<uint32_t>(seed_b[min((t + 1) * kTile - 1, m - 1)]);
+        static_cast<uint32_t>(seed_b[min((t + 1) * kChainTile - 1, m - 1)]);
     for (int h = 0; h < hops.k; ++h) {
       int64_t lo = 0, hi = hops.n[h];
       if (hops.table[h] != nullptr || hops.table32[h] != nullptr
@@ -1113,143 +1120,391 @@ __global__ void chain_tile_bounds(const int32_t* __restrict__ seed_b,
 }
 
 // LDS staging: a tile's src-0 window (avg ~|region|/n_tiles rows) is probed
-// by all 256 threads of the block — stage it through LDS once and search
-// there instead of hammering the same L1/L2 lines (guide: LDS-staged
-// probe structures).  16 KB leaves occupancy at 10 blocks/CU.
-constexpr int kChainLds = 4096;   // int32 rows: 16 KB, 10 blocks/CU
+// by all 256 threads of the block — stage it through LDS once and merge
+// there instead of hammering the same L1/L2 lines (guide: LDS-staged probe
+// structures).  At 16 KB + pad per block LDS never limits residency; the
+// kernel's registers do (6 blocks per CU as measured in round 3).
+constexpr int kChainLds = 4096;   // int32 rows a window may have to be staged
+// the 2 x b128 merge read may pass the window's end: the rows behind it
+// hold kChainPadKey, which no key compares above (a seed equal to it is
+// settled by the merge's search fallback)
+constexpr int kChainPad = 8;
+constexpr uint32_t kChainPadKey = 0xFFFFFFFFu;
+// window rows per thread that travel with the tile prefetch (in registers):
+// kChainPre * kBlock rows, one tile's worth when keys and seeds are 1:1;
+// the rest of a longer window is staged when the tile is processed
+constexpr int kChainPre = 4;
 
-// each thread owns kSub seeds of its tile (kTile = kSub * kBlock): the
-// independent probe chains per thread double the memory-level
-// parallelism, and the per-tile costs (window bounds, LDS staging
-// barriers) amortize over twice the seeds
-constexpr int kSub = kTile / kBlock;
+// everything a tile needs from global memory before its search can start;
+// loaded one tile ahead so the loop waits for HBM once per block, not once
+// per tile
+struct ChainTileIn {
+  uint32_t b[kChainSeeds], z[kChainSeeds];
+  uint32_t pw[kChainPre];
+};
 
-__global__ void chain_count_kernel(const int32_t* __restrict__ seed_b,
-                                   const int32_t* __restrict__ seed_z,
-                                   int64_t m, ChainHops hops,
-                                   const int64_t* __restrict__ win,
-                                   unsigned long long* __restrict__ total) {
-  __shared__ int32_t lds[kChainLds];
+// one tile's window of one hop: block-uniform, so it lives in scalar
+// registers and can be fetched two tiles ahead for free
+struct ChainWin {
+  int64_t lo, span;
+};
+
+__device__ __forceinline__ ChainWin chain_load_win(
+    const int64_t* __restrict__ win, int64_t t, int64_t m, int k, int h) {
+  ChainWin w{0, 0};
+  if (h >= 0 && t * kChainTile < m) {
+    w.lo = win[(t * k + h) * 2];
+    w.span = win[(t * k + h) * 2 + 1] - w.lo;
+  }
+  return w;
+}
+
+__device__ __forceinline__ bool chain_stages(int64_t wspan, int lds_min) {
+  return wspan > 0 && wspan <= kChainLds && wspan > lds_min;
+}
+
+// a thread's kChainSeeds consecutive seeds of one column.  `vec` is
+// block-uniform: a full tile behind a 16-byte aligned column pointer takes
+// one dwordx4; the tail tile and unaligned columns (a slice of a larger
+// tensor) take dword loads; seeds past the end read as 0 and their
+// contributions are dropped when the tile is summed.
+__device__ __forceinline__ void chain_load_seeds(
+    const int32_t* __restrict__ col, int64_t i0, int64_t m, bool vec,
+    uint32_t (&out)[kChainSeeds]) {
+  if (vec) {
+    uint4 v = *reinterpret_cast<const uint4*>(col + i0);
+    out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+  } else {
+#pragma unroll
+    for (int u = 0; u < kChainSeeds; ++u)
+      out[u] = i0 + u < m ? static_cast<uint32_t>(col[i0 + u]) : 0u;
+  }
+}
+
+__device__ __forceinline__ void chain_load_tile(
+    ChainTileIn& in, int64_t t, const int32_t* __restrict__ seed_b,
+    const int32_t* __restrict__ seed_z, int64_t m, const ChainHops& hops,
+    int hp, ChainWin w, bool b_vec, bool z_vec) {
+  int64_t i0 = t * kChainTile + threadIdx.x * kChainSeeds;
+  bool full = (t + 1) * kChainTile <= m;
+  chain_load_seeds(seed_b, i0, m, full && b_vec, in.b);
+  chain_load_seeds(seed_z, i0, m, full && z_vec, in.z);
+#pragma unroll
+  for (int j = 0; j < kChainPre; ++j) in.pw[j] = 0;
+  if (hp >= 0 && chain_stages(w.span, hops.lds_min)) {
+    // clamped, not predicated: no branch per row (rows past the window
+    // are replaced by the pad key when staged)
+    const int32_t* base = hops.key32[hp] + w.lo;
+    uint32_t n = static_cast<uint32_t>(w.span);
+#pragma unroll
+    for (int j = 0; j < kChainPre; ++j)
+      in.pw[j] = static_cast<uint32_t>(
+          base[min(threadIdx.x + j * kBlock, n - 1)]);
+  }
+}
+
+// stage window rows [r0 + tid, n) from global memory and the pad behind them
+__device__ __forceinline__ void chain_stage_rows(
+    uint32_t* lds, const int32_t* __restrict__ base, uint32_t n,
+    uint32_t r0) {
+  for (uint32_t r = r0 + threadIdx.x; r < n + kChainPad; r += kBlock) {
+    uint32_t v = kChainPadKey;
+    if (r < n) v = static_cast<uint32_t>(base[r]);
+    lds[r] = v;
+  }
+}
+
+// lower bound over a staged window (n >= 1) by bit descent: the largest
+// pos with w[pos - 1] < key.  The trip count follows from the window size
+// alone, so a wave stays converged; 32-bit indices throughout.
+__device__ __forceinline__ uint32_t lds_lower_bound_fixed(
+    const uint32_t* w, uint32_t n, uint32_t key) {
+  uint32_t pos = 0;
+  for (uint32_t step = 1u << (31 - __clz(static_cast<int>(n))); step > 0;
+       step >>= 1) {
+    uint32_t idx = pos + step;
+    uint32_t v = w[min(idx, n) - 1];
+    pos = (idx <= n) & (v < key) ? idx : pos;
+  }
+  return pos;
+}
+
+// plain bound in w[lo, hi) for the rare seeds the merge read cannot settle
+__device__ __forceinline__ uint32_t lds_bound(const uint32_t* w, uint32_t lo,
+                                              uint32_t hi, uint32_t key,
+                                              bool upper) {
+  while (lo < hi) {
+    uint32_t mid = (lo + hi) >> 1;
+    uint32_t v = w[mid];
+    if (upper ? v <= key : v < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// a hop's probe value: the seed's B component (src 0) or Z column (src 1).
+// A mask, not `?:` on the two arrays — that becomes a selected address and
+// sends the seed registers to scratch.
+__device__ __forceinline__ uint32_t chain_key(int32_t src, uint32_t b,
+                                              uint32_t z) {
+  uint32_t take_b = src == 0 ? 0xFFFFFFFFu : 0u;
+  return (b & take_b) | (z & ~take_b);
+}
+
+// first probe of a direct / table32 hop for all of a thread's seeds,
+// issued back to back and not waited for: the hop kind is one
+// block-uniform branch around the seed loop, and the direct table takes a
+// clamped index (its range check is applied when the probe is finished)
+__device__ __forceinline__ void chain_probe_issue(
+    const ChainHops& hops, int h, const ChainTileIn& in,
+    uint32_t (&raw)[kChainSeeds]) {
+  if (hops.direct[h] != nullptr) {
+    // dense-value hop: counts[v - dmin], coalesced across the wave
+#pragma unroll
+    for (int u = 0; u < kChainSeeds; ++u) {
+      uint64_t off = static_cast<uint64_t>(
+          static_cast<int64_t>(chain_key(hops.src[h], in.b[u], in.z[u]))
+          - hops.dmin[h]);
+      bool ok = off < static_cast<uint64_t>(hops.dlen[h]);
+      raw[u] = hops.direct[h][ok ? off : 0];
+    }
+    return;
+  }
+  // packed count-table hop: one 4-byte L2 load per seed
+  uint32_t mask = static_cast<uint32_t>(hops.tmask[h]);
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u)
+    raw[u] = hops.table32[h][
+        h32(chain_key(hops.src[h], in.b[u], in.z[u])) & mask];
+}
+
+// multiply the hop's counts into prod; only a hash collision loads again
+__device__ __forceinline__ void chain_probe_finish(
+    const ChainHops& hops, int h, const ChainTileIn& in,
+    const uint32_t (&raw)[kChainSeeds],
+    unsigned long long (&prod)[kChainSeeds]) {
+  if (hops.direct[h] != nullptr) {
+#pragma unroll
+    for (int u = 0; u < kChainSeeds; ++u) {
+      uint64_t off = static_cast<uint64_t>(
+          static_cast<int64_t>(chain_key(hops.src[h], in.b[u], in.z[u]))
+          - hops.dmin[h]);
+      prod[u] *= off < static_cast<uint64_t>(hops.dlen[h]) ? raw[u] : 0u;
+    }
+    return;
+  }
+  uint32_t mask = static_cast<uint32_t>(hops.tmask[h]);
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u) {
+    uint32_t v = chain_key(hops.src[h], in.b[u], in.z[u]);
+    uint32_t slot = h32(v) & mask;
+    uint32_t e = raw[u];
+    while (e != kTbl32Empty && (e >> 7) != v) {
+      slot = (slot + 1) & mask;
+      e = hops.table32[h][slot];
+    }
+    prod[u] *= e == kTbl32Empty ? 0u : (e & 0x7Fu);
+  }
+}
+
+// u64 count-table hop: one 8-byte L2 load per seed (vs log2(n) lines),
+// the four first probes issued together
+__device__ __forceinline__ void chain_table64_hop(
+    const ChainHops& hops, int h, const ChainTileIn& in,
+    unsigned long long (&prod)[kChainSeeds]) {
+  uint32_t mask = static_cast<uint32_t>(hops.tmask[h]);
+  unsigned long long raw[kChainSeeds];
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u)
+    raw[u] = hops.table[h][
+        h32(chain_key(hops.src[h], in.b[u], in.z[u])) & mask];
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u) {
+    uint32_t v = chain_key(hops.src[h], in.b[u], in.z[u]);
+    uint32_t slot = h32(v) & mask;
+    unsigned long long e = raw[u];
+    while (e != kTblEmpty && static_cast<uint32_t>(e >> 32) != v) {
+      slot = (slot + 1) & mask;
+      e = hops.table[h][slot];
+    }
+    prod[u] *= e == kTblEmpty ? 0ull : (e & 0xFFFFFFFFull);
+  }
+}
+
+__device__ __forceinline__ bool chain_hop_is_probe32(const ChainHops& hops,
+                                                     int h) {
+  return hops.direct[h] != nullptr || hops.table32[h] != nullptr;
+}
+
+// seeds are monotone: one lower bound for the thread's first seed, then
+// every seed of the thread is matched in registers against the 8 window
+// keys read from the 16-byte boundary below that bound.  All keys left of
+// a0 are < b[0] <= b[u], so a seed's matches start at a0 or later; when
+// the last key read is above the seed they also end before it, and the
+// count is the number of equal keys (pad keys are above such a seed).
+// Otherwise the run may go on past the 8 keys: search.  (A seed past the
+// end reads as 0 and counts nothing or garbage; its product is dropped.)
+__device__ __forceinline__ void chain_merge_lds(
+    const uint32_t* w, uint32_t n, const uint32_t (&b)[kChainSeeds],
+    unsigned long long (&prod)[kChainSeeds]) {
+  uint32_t lo0 = lds_lower_bound_fixed(w, n, b[0]);
+  uint32_t a0 = lo0 & ~3u;
+  uint4 w0 = *reinterpret_cast<const uint4*>(w + a0);
+  uint4 w1 = *reinterpret_cast<const uint4*>(w + a0 + 4);
+  uint32_t wv[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u) {
+    uint32_t key = b[u], cnt = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) cnt += wv[i] == key;
+    if (!(wv[7] > key)) {
+      uint32_t lo = lds_bound(w, a0, n, key, false);
+      cnt = lds_bound(w, lo, n, key, true) - lo;
+    }
+    prod[u] *= cnt;
+  }
+}
+
+// window too large for LDS (or not above lds_min), or a src-1 hop: search
+// global memory.  Off the hot path; region sizes are int64 by contract.
+__device__ __forceinline__ void chain_global_hop(
+    const int32_t* __restrict__ base, int64_t wspan, int32_t src,
+    const ChainTileIn& in, unsigned long long (&prod)[kChainSeeds]) {
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u) {
+    uint32_t key = chain_key(src, in.b[u], in.z[u]);
+    int64_t lo = lower_bound_u32(base, wspan, key);
+    // match runs are tiny (one object per subject in typical star data):
+    // walk forward a few cache-hot slots instead of paying a second full
+    // log2(wspan) dependent-load chain
+    int64_t hi = lo;
+    while (hi < wspan && hi - lo < 4
+           && static_cast<uint32_t>(base[hi]) == key) ++hi;
+    if (hi - lo == 4 && hi < wspan
+        && static_cast<uint32_t>(base[hi]) == key)
+      hi = lo + upper_bound_u32(base + lo, wspan - lo, key);
+    prod[u] *= static_cast<unsigned long long>(hi - lo);
+  }
+}
+
+// Tiles are software-pipelined.  While tile i is staged and merged, tile
+// i+1's seeds and window rows are in flight (its window bounds were
+// fetched an iteration earlier still), and tile i's first table probe is
+// issued before that work and consumed after it, so a block waits for
+// global memory once, not once per tile.  There are no per-seed
+// predicates: seeds past the end read as 0 and their products are dropped
+// when the tile is summed.
+__global__ void __launch_bounds__(kBlock)
+chain_count_kernel(const int32_t* __restrict__ seed_b,
+                   const int32_t* __restrict__ seed_z, int64_t m,
+                   ChainHops hops, const int64_t* __restrict__ win,
+                   unsigned long long* __restrict__ total) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kChainLds + kChainPad];
   unsigned long long acc = 0;
+  // hp: the src-0 window hop whose rows travel with the tile prefetch;
+  // ht: the table hop whose first probe is issued ahead of the window work
+  int hp = -1, ht = -1;
+  for (int h = hops.k - 1; h >= 0; --h) {
+    if (chain_hop_is_probe32(hops, h)) ht = h;
+    else if (hops.table[h] == nullptr && hops.src[h] == 0) hp = h;
+  }
+  bool b_vec = (reinterpret_cast<uintptr_t>(seed_b) & 15) == 0;
+  bool z_vec = (reinterpret_cast<uintptr_t>(seed_z) & 15) == 0;
   // block-uniform tile iteration (every thread of the block is in the same
-  // tile) so the cooperative LDS loads can barrier safely
-  for (int64_t t = blockIdx.x; t * kTile < m; t += gridDim.x) {
-    uint32_t b_c[kSub], z_c[kSub];
-    bool act[kSub];
-    unsigned long long prod[kSub];
-    for (int u = 0; u < kSub; ++u) {
-      int64_t i = t * kTile + u * kBlock + threadIdx.x;
-      act[u] = i < m;
-      b_c[u] = act[u] ? static_cast<uint32_t>(seed_b[i]) : 0;
-      z_c[u] = act[u] ? static_cast<uint32_t>(seed_z[i]) : 0;
-      prod[u] = 1;
+  // tile, and every staging decision reads block-uniform values) so the
+  // cooperative LDS loads can barrier safely
+  const int64_t step = gridDim.x;
+  int64_t t = blockIdx.x;
+  ChainTileIn cur = {}, nxt = {};
+  ChainWin w_cur = chain_load_win(win, t, m, hops.k, hp);
+  ChainWin w_nxt = chain_load_win(win, t + step, m, hops.k, hp);
+  if (t * kChainTile < m)
+    chain_load_tile(cur, t, seed_b, seed_z, m, hops, hp, w_cur, b_vec,
+                    z_vec);
+  for (; t * kChainTile < m; t += step) {
+    unsigned long long prod[kChainSeeds];
+    uint32_t raw[kChainSeeds];
+#pragma unroll
+    for (int u = 0; u < kChainSeeds; ++u) prod[u] = 1;
+    // the prefetched hop goes first: its rows leave the registers for LDS
+    // before the next tile's loads claim theirs, and before the table
+    // probe is issued, so that writing them waits for nothing newer
+    bool staged = hp >= 0 && chain_stages(w_cur.span, hops.lds_min);
+    uint32_t n_cur = static_cast<uint32_t>(w_cur.span);
+    if (staged) {
+#pragma unroll
+      for (int j = 0; j < kChainPre; ++j) {
+        uint32_t r = threadIdx.x + j * kBlock;
+        lds[r] = r < n_cur ? cur.pw[j] : kChainPadKey;
+      }
+      chain_stage_rows(lds, hops.key32[hp] + w_cur.lo, n_cur,
+                       kChainPre * kBlock);
     }
-    // no early exit: the hop searches are independent dependent-load
-    // chains — letting them all issue gives the scheduler ILP to hide
-    // L2 latency
-    for (int h = 0; h < hops.k; ++h) {
-      if (hops.direct[h] != nullptr) {
-        // dense-value hop: counts[v - dmin], coalesced across the wave
-        for (int u = 0; u < kSub; ++u) {
-          if (!act[u]) continue;
-          uint32_t v = hops.src[h] == 0 ? b_c[u] : z_c[u];
-          uint64_t off = static_cast<uint64_t>(
-              static_cast<int64_t>(v) - hops.dmin[h]);
-          prod[u] *= off < static_cast<uint64_t>(hops.dlen[h])
-                         ? hops.direct[h][off] : 0u;
-        }
-        continue;
-      }
-      if (hops.table32[h] != nullptr) {
-        // packed count-table hop: one 4-byte L2 load per seed
-        uint32_t mask = static_cast<uint32_t>(hops.tmask[h]);
-        for (int u = 0; u < kSub; ++u) {
-          if (!act[u]) continue;
-          uint32_t v = hops.src[h] == 0 ? b_c[u] : z_c[u];
-          uint32_t slot = h32(v) & mask;
-          unsigned long long cnt = 0;
-          for (;;) {
-            uint32_t e = hops.table32[h][slot];
-            if (e == kTbl32Empty) break;
-            if ((e >> 7) == v) {
-              cnt = e & 0x7Fu;
-              break;
-            }
-            slot = (slot + 1) & mask;
-          }
-          prod[u] *= cnt;
-        }
-        continue;
-      }
+    if (ht >= 0) chain_probe_issue(hops, ht, cur, raw);
+    if ((t + step) * kChainTile < m)
+      chain_load_tile(nxt, t + step, seed_b, seed_z, m, hops, hp, w_nxt,
+                      b_vec, z_vec);
+    ChainWin w_far = chain_load_win(win, t + 2 * step, m, hops.k, hp);
+    // hops in order, rotated so that the prefetched hop (already in LDS)
+    // comes first
+    for (int j = 0; j < hops.k; ++j) {
+      int h = j + max(hp, 0);
+      if (h >= hops.k) h -= hops.k;
+      if (h == ht) continue;
       if (hops.table[h] != nullptr) {
-        // count-table hop: one 8-byte L2 load (vs log2(n) lines)
-        uint32_t mask = static_cast<uint32_t>(hops.tmask[h]);
-        for (int u = 0; u < kSub; ++u) {
-          if (!act[u]) continue;
-          uint32_t v = hops.src[h] == 0 ? b_c[u] : z_c[u];
-          uint32_t slot = h32(v) & mask;
-          unsigned long long cnt = 0;
-          for (;;) {
-            unsigned long long e = hops.table[h][slot];
-            if (e == kTblEmpty) break;
-            if (static_cast<uint32_t>(e >> 32) == v) {
-              cnt = e & 0xFFFFFFFFull;
-              break;
-            }
-            slot = (slot + 1) & mask;
-          }
-          prod[u] *= cnt;
-        }
+        chain_table64_hop(hops, h, cur, prod);
         continue;
       }
-      int64_t wlo = win[(t * hops.k + h) * 2];
-      int64_t wspan = win[(t * hops.k + h) * 2 + 1] - wlo;
-      const int32_t* base = hops.key32[h] + wlo;
-      if (hops.src[h] == 0 && wspan <= kChainLds
-          && wspan > hops.lds_min) {
-        // cooperative stage + barrier: search LDS, not HBM/L2
-        for (int64_t j = threadIdx.x; j < wspan; j += blockDim.x)
-          lds[j] = base[j];
+      if (chain_hop_is_probe32(hops, h)) {
+        uint32_t r2[kChainSeeds];
+        chain_probe_issue(hops, h, cur, r2);
+        chain_probe_finish(hops, h, cur, r2, prod);
+        continue;
+      }
+      ChainWin w = h == hp ? w_cur : chain_load_win(win, t, m, hops.k, h);
+      const int32_t* base = hops.key32[h] + w.lo;
+      if (hops.src[h] == 0 && chain_stages(w.span, hops.lds_min)) {
+        // cooperative stage + barrier: merge in LDS, not HBM/L2
+        uint32_t n = static_cast<uint32_t>(w.span);
+        if (h != hp) chain_stage_rows(lds, base, n, 0);
         __syncthreads();
-        for (int u = 0; u < kSub; ++u) {
-          if (!act[u]) continue;
-          uint32_t key = hops.src[h] == 0 ? b_c[u] : z_c[u];
-          int64_t lo = lower_bound_u32(lds, wspan, key);
-          int64_t hi = lo;
-          while (hi < wspan && hi - lo < 4
-                 && static_cast<uint32_t>(lds[hi]) == key) ++hi;
-          if (hi - lo == 4 && hi < wspan
-              && static_cast<uint32_t>(lds[hi]) == key)
-            hi = lo + upper_bound_u32(lds + lo, wspan - lo, key);
-          prod[u] *= static_cast<unsigned long long>(hi - lo);
-        }
-        __syncthreads();  // before the next hop reuses the buffer
+        chain_merge_lds(lds, n, cur.b, prod);
+        __syncthreads();  // before the next hop or tile reuses the buffer
         continue;
       }
-      for (int u = 0; u < kSub; ++u) {
-        if (!act[u]) continue;
-        uint32_t key = hops.src[h] == 0 ? b_c[u] : z_c[u];
-        int64_t lo = lower_bound_u32(base, wspan, key);
-        // match runs are tiny (one object per subject in typical star
-        // data): walk forward a few cache-hot slots instead of paying a
-        // second full log2(wspan) dependent-load chain
-        int64_t hi = lo;
-        while (hi < wspan && hi - lo < 4
-               && static_cast<uint32_t>(base[hi]) == key) ++hi;
-        if (hi - lo == 4 && hi < wspan
-            && static_cast<uint32_t>(base[hi]) == key)
-          hi = lo + upper_bound_u32(base + lo, wspan - lo, key);
-        prod[u] *= static_cast<unsigned long long>(hi - lo);
-      }
+      chain_global_hop(base, w.span, hops.src[h], cur, prod);
     }
-    for (int u = 0; u < kSub; ++u)
-      if (act[u]) acc += prod[u];
+    if (ht >= 0) chain_probe_finish(hops, ht, cur, raw, prod);
+    int64_t i0 = t * kChainTile + threadIdx.x * kChainSeeds;
+#pragma unroll
+    for (int u = 0; u < kChainSeeds; ++u)
+      acc += i0 + u < m ? prod[u] : 0ull;
+    cur = nxt;
+    w_cur = w_nxt;
+    w_nxt = w_far;
   }
   // wave reduction then one device-scope atomic per wave (guide G12)
   for (int off = 32; off > 0; off >>= 1)
     acc += __shfl_down(acc, off);
   if ((threadIdx.x & 63) == 0 && acc)
     atomicAdd(total, acc);
+}
+
+// One block per tile up to what the device keeps resident at once (asked of
+// the runtime, since it follows the kernel's register count); the rest
+// grid-stride, which is what the tile pipeline overlaps.  All blocks start
+// together, so none queues behind a full first round.
+inline int chain_grid(int64_t n_tiles) {
+  static const int resident = [] {
+    int per_cu = 0, dev = 0, cus = 0;
+    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &per_cu, chain_count_kernel, kBlock, 0));
+    HIP_OK(hipGetDevice(&dev));
+    HIP_OK(hipDeviceGetAttribute(
+        &cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return std::max(1, per_cu * cus);
+  }();
+  return static_cast<int>(
+      std::max<int64_t>(1, std::min<int64_t>(n_tiles, resident)));
 }
 
 // Capture-friendly variant: caller owns the window + total buffers, no
@@ -1294,7 +1549,7 @@ void chain_count_into(at::Tensor seed_b, at::Tensor seed_z,
   auto stream = cur_stream();
   total.zero_();
   if (m == 0) return;
-  int64_t n_tiles = (m + kTile - 1) / kTile;
+  int64_t n_tiles = (m + kChainTile - 1) / kChainTile;
   TORCH_CHECK(win.numel() >= n_tiles * hops.k * 2, "win buffer too small");
   hipLaunchKernelGGL(chain_tile_bounds, dim3(grid_for(n_tiles)),
                      dim3(kBlock), 0, stream,
@@ -1302,8 +1557,8 @@ void chain_count_into(at::Tensor seed_b, at::Tensor seed_z,
                      win.data_ptr<int64_t>(),
                      static_cast<unsigned long long*>(nullptr));
   HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(chain_count_kernel, dim3(grid_for(m)), dim3(kBlock), 0,
-                     stream, seed_b.data_ptr<int32_t>(),
+  hipLaunchKernelGGL(chain_count_kernel, dim3(chain_grid(n_tiles)),
+                     dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
                      seed_z.data_ptr<int32_t>(), m, hops,
                      win.data_ptr<int64_t>(),
                      reinterpret_cast<unsigned long long*>(
@@ -1338,8 +1593,16 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
   TORCH_CHECK(seed_b.is_cuda() && seed_b.dtype() == at::kInt
               && seed_z.is_cuda());
   auto cs = std::make_unique<ChainServe>();
-  cs->seed_b = seed_b;
-  cs->seed_z = seed_z;
+  // the kernel reads each seed column with dwordx4 when its pointer is
+  // 16-byte aligned; seed_z usually arrives as a slice of the PSO column,
+  // aligned to 4 bytes only.  The seeds are immutable for this
+  // registration's lifetime, so take an aligned copy once here.
+  auto aligned16 = [](const at::Tensor& x) {
+    bool ok = reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0;
+    return ok ? x : x.clone();
+  };
+  cs->seed_b = aligned16(seed_b);
+  cs->seed_z = aligned16(seed_z);
   cs->m = seed_b.numel();
   if (const char* e = getenv("KOLIBRIE_CHAIN_LDS_MIN"))
     cs->hops.lds_min = atoi(e);
@@ -1368,7 +1631,7 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
       cs->hops.tmask[h] = hop_table[h].numel() - 1;
     }
   }
-  cs->n_tiles = (cs->m + kTile - 1) / kTile;
+  cs->n_tiles = (cs->m + kChainTile - 1) / kChainTile;
   cs->win = at::empty({std::max<int64_t>(1, cs->n_tiles * cs->hops.k * 2)},
                       seed_b.options().dtype(at::kLong));
   // total[0] = accumulator, total[1] = constant 1 (the completion flag's
@@ -1404,8 +1667,8 @@ int64_t serve_chain_count(int64_t id) {
   *flag = 0;
   // windows were precomputed at registration; the accumulator was zeroed
   // there (first call) or by the post-readback memset of the previous call
-  hipLaunchKernelGGL(chain_count_kernel, dim3(grid_for(cs.m)), dim3(kBlock),
-                     0, stream, cs.seed_b.data_ptr<int32_t>(),
+  hipLaunchKernelGGL(chain_count_kernel, dim3(chain_grid(cs.n_tiles)),
+                     dim3(kBlock), 0, stream, cs.seed_b.data_ptr<int32_t>(),
                      cs.seed_z.data_ptr<int32_t>(), cs.m, cs.hops,
                      cs.win.data_ptr<int64_t>(),
                      reinterpret_cast<unsigned long long*>(total_ptr));
@@ -1478,7 +1741,7 @@ int64_t chain_count(at::Tensor seed_b, at::Tensor seed_z,
   auto total = at::zeros({1}, seed_b.options().dtype(at::kLong));
   if (m > 0) {
     auto stream = cur_stream();
-    int64_t n_tiles = (m + kTile - 1) / kTile;
+    int64_t n_tiles = (m + kChainTile - 1) / kChainTile;
     auto win = at::empty({n_tiles * hops.k * 2},
                          seed_b.options().dtype(at::kLong));
     hipLaunchKernelGGL(chain_tile_bounds, dim3(grid_for(n_tiles)),
@@ -1487,8 +1750,8 @@ int64_t chain_count(at::Tensor seed_b, at::Tensor seed_z,
                        win.data_ptr<int64_t>(),
                        static_cast<unsigned long long*>(nullptr));
     HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(chain_count_kernel, dim3(grid_for(m)), dim3(kBlock), 0,
-                       stream, seed_b.data_ptr<int32_t>(),
+    hipLaunchKernelGGL(chain_count_kernel, dim3(chain_grid(n_tiles)),
+                       dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
                        seed_z.data_ptr<int32_t>(), m, hops,
                        win.data_ptr<int64_t>(),
                        reinterpret_cast<unsigned long long*>(
@@ -3828,7 +4091,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K1 scan-probe, leading-component range -> (li, b, z)");
   m.def("hash_join", &hash_join,
         "K2 chained hash join over int32 key columns -> (li, ri)");
-  m.def("chain_tile", []() { return static_cast<int64_t>(kTile); },
+  m.def("chain_tile", []() { return static_cast<int64_t>(kChainTile); },
         "seed rows per chain tile (win buffer sizing)");
   m.def("chain_count", &chain_count,
         "fused COUNT(*) over a seed scan + probe-hop chain",
