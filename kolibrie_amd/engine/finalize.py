@@ -67,16 +67,7 @@ def finalize_select_bindings(select: SelectQuery, rows: Bindings, db
         cols = [rows.col(v) for v in proj_names]
         if select.order_by:
             # stable distinct preserving order: keep first occurrence
-            gid, _ = group_index(cols)
-            first = torch.zeros(rows.n, dtype=torch.bool, device=dev)
-            seen: Dict[int, bool] = {}
-            gl = gid.cpu().tolist()
-            keep_idx = []
-            for i, g in enumerate(gl):
-                if g not in seen:
-                    seen[g] = True
-                    keep_idx.append(i)
-            rows = rows.gather(torch.tensor(keep_idx, dtype=torch.long, device=dev))
+            rows = rows.gather(_first_occurrences(cols))
         else:
             uc = unique_rows(cols)
             rows = Bindings(dict(zip(proj_names, uc)),
@@ -90,14 +81,49 @@ def finalize_select_bindings(select: SelectQuery, rows: Bindings, db
     return rows
 
 
+def _first_occurrences(cols) -> torch.Tensor:
+    """Ascending row indices of the first occurrence of every distinct row
+    of `cols` (stable DISTINCT: the rows kept and their order are those of a
+    front-to-back scan with a seen-set); runs on the columns' device."""
+    n = cols[0].numel()
+    dev = cols[0].device
+    gid, ng = group_index(cols)
+    first = torch.full((ng,), n, dtype=torch.long, device=dev)
+    first.scatter_reduce_(0, gid,
+                          torch.arange(n, dtype=torch.long, device=dev),
+                          reduce="amin")
+    return torch.sort(first).values
+
+
 def _order_perm(select: SelectQuery, rows: Bindings, db) -> torch.Tensor:
+    from . import collation
     dev = rows.device
     perm = torch.arange(rows.n, dtype=torch.long, device=dev)
+    on_device = dev.type == "cuda" and rows.n >= collation.DEVICE_MIN_ROWS
     for cond in reversed(select.order_by):
         if not rows.has(cond.var):
             continue
         ids = rows.col(cond.var)[perm]
         ids_u = ids.to(torch.int64) & 0xFFFFFFFF
+        if on_device:
+            # K11: numeric-vs-lexical and the collation ranks both come from
+            # the device term-text table; no id column goes to the host
+            numeric, ranks = collation.order_key(db, ids)
+            if numeric:
+                from .tensor_utils import values_for_ids
+                vals = values_for_ids(db.value_column(), ids_u)
+                key = torch.argsort(vals, stable=True,
+                                    descending=cond.descending)
+            else:
+                # stable descending keeps equal keys in input order, as
+                # sorted(reverse=True) does on the host path
+                key = torch.argsort(ranks, stable=True,
+                                    descending=cond.descending)
+            perm = perm[key]
+            continue
+        collation.last_device_stats.clear()
+        collation.last_device_stats.update(path="host", distinct=None,
+                                           rounds=0, undecided=0)
         strs = [db.dictionary.decode(int(x)) or "" for x in ids_u.cpu().tolist()]
         all_numeric = all(_is_num(s) for s in strs) and len(strs) > 0
         if all_numeric:

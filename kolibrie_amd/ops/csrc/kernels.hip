@@ -13,6 +13,10 @@
 //   K9 str_match   — STRSTARTS / STRENDS / CONTAINS / literal REGEX over the
 //                    device term-text table (the reference evaluates these
 //                    to false).
+//   K11 term_order — ORDER BY collation: per-round sort keys, common-prefix
+//                    skip and numeric classification over the term-text
+//                    table (replaces the per-row decode + sorted() of
+//                    execute_query.rs:477's port).
 //
 // Design notes (per CDNA4 guide): wave64, 256-thread blocks, grid-stride
 // loops capped so the 256-CU chip is saturated without oversubscription;
@@ -790,6 +794,182 @@ __global__ void str_match_long(const int32_t* __restrict__ ids,
       }
     }
     if (lane == 0) out[row] = r;
+  }
+}
+
+// ------------------------------------------------------ K11 term_order kernels
+// ORDER BY collation over the device term-text table.  Python orders str by
+// code point and UTF-8 byte order is code-point order, so a bytewise order of
+// the term text is the order sorted() gives.  The host side
+// (engine/collation.py) refines groups of terms most-significant-bytes first;
+// these kernels supply one round's sort keys, the common-prefix skip and the
+// numeric-vs-lexical classification.  One lane per element; text is read
+// only through str_window / str_ld_q; an id outside [0, V) (unbound, quoted,
+// past the vocabulary) or with a corrupt table entry is the empty string.
+constexpr int64_t kLcpSentinel = int64_t(1) << 62;
+
+// start byte and byte length of term `id`, (0, 0) for anything unreadable
+__device__ __forceinline__ void term_span(int32_t id, int64_t V,
+                                          const int64_t* __restrict__ offsets,
+                                          int64_t cap, int64_t* start,
+                                          int64_t* len) {
+  *start = 0;
+  *len = 0;
+  if (id < 0 || id >= V) return;
+  int64_t s = offsets[id];
+  int64_t e = offsets[id + 1];
+  if (s < 0 || e < s || e > cap) return;
+  *start = s;
+  *len = e - s;
+}
+
+// bytes left in a term of `len` bytes from byte `depth` on (0 when past it)
+__device__ __forceinline__ int64_t term_rest(int64_t len, int64_t depth) {
+  if (depth < 0) depth = 0;
+  return depth >= len ? 0 : len - depth;
+}
+
+// Sort key of the 7 bytes at depth[i]: bytes big-endian in bits 63..8 (zeros
+// past the term's end), count of real bytes (0..7) in the low byte, sign bit
+// flipped so a SIGNED sort orders the keys as unsigned.  The count byte puts
+// a term before every longer term it is a prefix of, NUL bytes included.
+__global__ void term_chunk_keys_kernel(const int32_t* __restrict__ ids,
+                                       const int64_t* __restrict__ depth,
+                                       int64_t m,
+                                       const uint8_t* __restrict__ bytes,
+                                       int64_t cap,
+                                       const int64_t* __restrict__ offsets,
+                                       int64_t V, int64_t* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t start, len;
+    term_span(ids[i], V, offsets, cap, &start, &len);
+    int64_t d = depth[i];
+    int64_t rest = term_rest(len, d);
+    int64_t cnt = rest < 7 ? rest : 7;
+    uint64_t key = 0;
+    if (cnt > 0) {
+      uint64_t w = str_window(bytes, start + d, cap) & str_byte_mask(cnt);
+      key = __builtin_bswap64(w);    // byte 0 -> bits 63..56; byte 7 masked off
+    }
+    key |= static_cast<uint64_t>(cnt);
+    out[i] = static_cast<int64_t>(key ^ 0x8000000000000000ull);
+  }
+}
+
+// Common-prefix length of terms i-1 and i measured from depth[i], for rows
+// with same_group[i]; the sentinel for row 0 and for group heads.
+__global__ void term_adjacent_lcp_kernel(const int32_t* __restrict__ ids,
+                                         const int64_t* __restrict__ depth,
+                                         const bool* __restrict__ same_group,
+                                         int64_t m,
+                                         const uint8_t* __restrict__ bytes,
+                                         int64_t cap,
+                                         const int64_t* __restrict__ offsets,
+                                         int64_t V,
+                                         int64_t* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    if (i == 0 || !same_group[i]) {
+      out[i] = kLcpSentinel;
+      continue;
+    }
+    int64_t sa, la, sb, lb;
+    term_span(ids[i - 1], V, offsets, cap, &sa, &la);
+    term_span(ids[i], V, offsets, cap, &sb, &lb);
+    int64_t d = depth[i];
+    if (d < 0) d = 0;
+    int64_t ra = term_rest(la, d);
+    int64_t rb = term_rest(lb, d);
+    int64_t lim = ra < rb ? ra : rb;
+    int64_t k = 0;
+    for (; k < lim; k += 8) {
+      uint64_t x = (str_window(bytes, sa + d + k, cap)
+                    ^ str_window(bytes, sb + d + k, cap))
+                   & str_byte_mask(lim - k);
+      if (x) {
+        k += __builtin_ctzll(x) >> 3;
+        break;
+      }
+    }
+    out[i] = k < lim ? k : lim;
+  }
+}
+
+// Decimal-literal automaton for [+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?
+enum NumState : int {
+  NS_START = 0, NS_SIGN, NS_INT, NS_DOT, NS_FRAC, NS_E, NS_ESIGN, NS_EXP,
+  NS_DEAD
+};
+
+__device__ __forceinline__ int num_step(int st, uint8_t b) {
+  bool digit = b >= '0' && b <= '9';
+  bool sign = b == '+' || b == '-';
+  bool dot = b == '.';
+  bool e = b == 'e' || b == 'E';
+  switch (st) {
+    case NS_START: return digit ? NS_INT : sign ? NS_SIGN : dot ? NS_DOT
+                                                                : NS_DEAD;
+    case NS_SIGN:  return digit ? NS_INT : dot ? NS_DOT : NS_DEAD;
+    case NS_INT:   return digit ? NS_INT : dot ? NS_FRAC : e ? NS_E : NS_DEAD;
+    case NS_DOT:   return digit ? NS_FRAC : NS_DEAD;
+    case NS_FRAC:  return digit ? NS_FRAC : e ? NS_E : NS_DEAD;
+    case NS_E:     return digit ? NS_EXP : sign ? NS_ESIGN : NS_DEAD;
+    case NS_ESIGN: return digit ? NS_EXP : NS_DEAD;
+    case NS_EXP:   return digit ? NS_EXP : NS_DEAD;
+    default:       return NS_DEAD;
+  }
+}
+
+// a printable ASCII byte that no string accepted by Python's float() holds
+__device__ __forceinline__ bool num_forbidden(uint8_t b) {
+  if (b < 0x21 || b > 0x7e) return false;
+  if (b >= '0' && b <= '9') return false;
+  switch (b) {
+    case '+': case '-': case '.': case '_':
+    case 'e': case 'a': case 'f': case 'i': case 'n': case 't': case 'y':
+    case 'E': case 'A': case 'F': case 'I': case 'N': case 'T': case 'Y':
+      return false;
+    default:
+      return true;
+  }
+}
+
+// 1 = the whole term is a decimal literal (float() accepts), 0 = empty,
+// unreadable id or a forbidden byte (float() rejects), 2 = undecided: the
+// host applies Python's own rules (padding, underscores, nan/inf, non-ASCII
+// digits).
+__global__ void term_numeric_class_kernel(const int32_t* __restrict__ ids,
+                                          int64_t m,
+                                          const uint8_t* __restrict__ bytes,
+                                          int64_t cap,
+                                          const int64_t* __restrict__ offsets,
+                                          int64_t V,
+                                          uint8_t* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t start, len;
+    term_span(ids[i], V, offsets, cap, &start, &len);
+    if (len == 0) {
+      out[i] = 0;
+      continue;
+    }
+    int st = NS_START;
+    bool forbidden = false;
+    for (int64_t p = 0; p < len && !forbidden; p += 8) {
+      uint64_t w = str_window(bytes, start + p, cap);
+      int nb = len - p < 8 ? static_cast<int>(len - p) : 8;
+      for (int k = 0; k < nb; ++k) {
+        uint8_t b = static_cast<uint8_t>(w >> (8 * k));
+        st = num_step(st, b);
+        if (num_forbidden(b)) {
+          forbidden = true;
+          break;
+        }
+      }
+    }
+    bool accept = st == NS_INT || st == NS_FRAC || st == NS_EXP;
+    out[i] = forbidden ? 0 : accept ? 1 : 2;
   }
 }
 
@@ -2208,6 +2388,94 @@ py::tuple str_match(at::Tensor ids, at::Tensor bytes, at::Tensor offsets,
     HIP_OK(hipGetLastError());
   }
   return py::make_tuple(out, ovf_count);
+}
+
+// K11 term_order wrappers.  Shared argument checks; returns the text base
+// pointer (null for an empty blob, which no lane then reads: cap == 0).
+static const uint8_t* term_order_check(const char* who, const at::Tensor& ids,
+                                       const at::Tensor& bytes,
+                                       const at::Tensor& offsets, int64_t V) {
+  TORCH_CHECK(ids.is_cuda() && ids.dtype() == at::kInt && ids.dim() == 1
+              && ids.is_contiguous(), who, ": ids must be int32 on device");
+  TORCH_CHECK(bytes.is_cuda() && bytes.dtype() == at::kByte
+              && bytes.dim() == 1 && bytes.is_contiguous(),
+              who, ": bytes must be uint8");
+  TORCH_CHECK(offsets.is_cuda() && offsets.dtype() == at::kLong
+              && offsets.dim() == 1 && offsets.is_contiguous(),
+              who, ": offsets must be int64");
+  TORCH_CHECK(bytes.device() == ids.device()
+              && offsets.device() == ids.device(),
+              who, ": tensors on different devices");
+  TORCH_CHECK(V >= 0 && offsets.numel() >= V + 1,
+              who, ": offsets shorter than V + 1");
+  const uint8_t* bp = bytes.numel() ? bytes.data_ptr<uint8_t>() : nullptr;
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(bp) % 8 == 0,
+              who, ": text must be 8-byte aligned");
+  return bp;
+}
+
+static void term_order_check_depth(const char* who, const at::Tensor& ids,
+                                   const at::Tensor& depth) {
+  TORCH_CHECK(depth.is_cuda() && depth.dtype() == at::kLong
+              && depth.dim() == 1 && depth.is_contiguous()
+              && depth.numel() == ids.numel()
+              && depth.device() == ids.device(),
+              who, ": depth must be int64[m] on the ids' device");
+}
+
+at::Tensor term_chunk_keys(at::Tensor ids, at::Tensor depth, at::Tensor bytes,
+                           at::Tensor offsets, int64_t V) {
+  const uint8_t* bp = term_order_check("term_chunk_keys", ids, bytes, offsets,
+                                       V);
+  term_order_check_depth("term_chunk_keys", ids, depth);
+  const int64_t m = ids.numel();
+  auto out = at::empty({m}, ids.options().dtype(at::kLong));
+  if (m == 0) return out;
+  hipLaunchKernelGGL(term_chunk_keys_kernel, dim3(grid_for(m)), dim3(kBlock),
+                     0, cur_stream(), ids.data_ptr<int32_t>(),
+                     depth.data_ptr<int64_t>(), m, bp, bytes.numel(),
+                     offsets.data_ptr<int64_t>(), V, out.data_ptr<int64_t>());
+  HIP_OK(hipGetLastError());
+  return out;
+}
+
+at::Tensor term_adjacent_lcp(at::Tensor ids, at::Tensor depth,
+                             at::Tensor same_group, at::Tensor bytes,
+                             at::Tensor offsets, int64_t V) {
+  const uint8_t* bp = term_order_check("term_adjacent_lcp", ids, bytes,
+                                       offsets, V);
+  term_order_check_depth("term_adjacent_lcp", ids, depth);
+  TORCH_CHECK(same_group.is_cuda() && same_group.dtype() == at::kBool
+              && same_group.dim() == 1 && same_group.is_contiguous()
+              && same_group.numel() == ids.numel()
+              && same_group.device() == ids.device(),
+              "term_adjacent_lcp: same_group must be bool[m] on the ids' "
+              "device");
+  const int64_t m = ids.numel();
+  auto out = at::empty({m}, ids.options().dtype(at::kLong));
+  if (m == 0) return out;
+  hipLaunchKernelGGL(term_adjacent_lcp_kernel, dim3(grid_for(m)),
+                     dim3(kBlock), 0, cur_stream(), ids.data_ptr<int32_t>(),
+                     depth.data_ptr<int64_t>(), same_group.data_ptr<bool>(),
+                     m, bp, bytes.numel(), offsets.data_ptr<int64_t>(), V,
+                     out.data_ptr<int64_t>());
+  HIP_OK(hipGetLastError());
+  return out;
+}
+
+at::Tensor term_numeric_class(at::Tensor ids, at::Tensor bytes,
+                              at::Tensor offsets, int64_t V) {
+  const uint8_t* bp = term_order_check("term_numeric_class", ids, bytes,
+                                       offsets, V);
+  const int64_t m = ids.numel();
+  auto out = at::empty({m}, ids.options().dtype(at::kByte));
+  if (m == 0) return out;
+  hipLaunchKernelGGL(term_numeric_class_kernel, dim3(grid_for(m)),
+                     dim3(kBlock), 0, cur_stream(), ids.data_ptr<int32_t>(),
+                     m, bp, bytes.numel(), offsets.data_ptr<int64_t>(), V,
+                     out.data_ptr<uint8_t>());
+  HIP_OK(hipGetLastError());
+  return out;
 }
 
 // ------------------------------------------------- host bulk N-Triples parse
@@ -4133,6 +4401,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("str_long_threshold",
         []() { return static_cast<int64_t>(kStrLongThreshold); },
         "term length above which CONTAINS rows take the long-term kernel");
+  m.def("term_chunk_keys", &term_chunk_keys,
+        "K11 7-byte big-endian sort key + count byte of each term at its "
+        "depth -> int64 (sign-flipped)");
+  m.def("term_adjacent_lcp", &term_adjacent_lcp,
+        "K11 common-prefix length of neighbouring terms of one group, "
+        "measured from depth -> int64 (sentinel at group heads)");
+  m.def("term_lcp_sentinel",
+        []() { return static_cast<int64_t>(kLcpSentinel); },
+        "value term_adjacent_lcp returns for group heads");
+  m.def("term_numeric_class", &term_numeric_class,
+        "K11 decimal-literal class per term -> uint8 (0 no, 1 yes, "
+        "2 undecided)");
   m.def("vocab_pack_bytes", &vocab_pack_bytes,
         "annex terms packed as (uint8 blob, int64 lengths)");
 }

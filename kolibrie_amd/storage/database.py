@@ -223,7 +223,7 @@ class SparqlDatabase:
         self._value_col_cache: Optional[torch.Tensor] = None
         self._value_col_len = 0
         # device term-text table; stays None until the first FILTER string
-        # predicate asks for it (term_text())
+        # predicate or device ORDER BY asks for it (term_text())
         self._term_text_cache: Optional[_TermText] = None
 
     # ------------------------------------------------------------------ terms
@@ -494,12 +494,25 @@ class SparqlDatabase:
         """Device-resident UTF-8 of every plain term: `(bytes_u8,
         offsets_i64)` with term i at `bytes[offsets[i]:offsets[i+1]]`.
 
-        Built on the first FILTER string predicate and not before.  The
+        Built on the first FILTER string predicate, or the first ORDER BY
+        that runs on the GPU (`term_ranks`), and not before.  The
         dictionary is append-only, so when it has grown only the new tail
         is packed and uploaded, into buffers whose capacity doubles; the
         bytes already on the device are never re-packed.  Costs the
         vocabulary's UTF-8 size + 8 bytes per term of device memory."""
         return device_term_text(self)
+
+    def term_ranks(self, ids: torch.Tensor) -> torch.Tensor:
+        """Collation rank (int64) of every element of the id column `ids`,
+        dense over the column's distinct terms, in the order ORDER BY and
+        Python's `sorted()` give strings: by code point.  Ids without text
+        (UNBOUND, quoted triples, unknown ids) rank with "".
+
+        Computed from the term-text table by engine/collation.rank_terms
+        (the K11 kernels on a GPU), so the first call builds that table:
+        the same opt-in cost as the first FILTER string predicate."""
+        from ..engine.collation import rank_terms
+        return rank_terms(self, ids)
 
     # --------------------------------------------------------- quoted columns
     def quoted_columns(self):

@@ -14,7 +14,8 @@ packed UTF-8 copy of every term (`pack_text` below) for the `str_match`
 kernel.  It costs the vocabulary's UTF-8 size plus 8 bytes per term of
 device memory (up to 2x while a doubling reallocation is in flight) and is
 extended append-only; a database that never runs a string predicate never
-builds it.
+builds it.  ORDER BY on a GPU reads the same table (engine/collation.py) and
+builds it on first use.
 
 RDF-star quoted triples are interned with bit 31 set
 (ref: shared/src/quoted_triple_store.rs:17-80) and recurse on encode/decode
