@@ -1262,11 +1262,16 @@ at::Tensor build_count_table(at::Tensor packed_entries) {
   return table;
 }
 
-// The chain kernel's own tile: each thread owns kChainSeeds CONSECUTIVE
-// seeds (one dwordx4 per seed column), a block owns kChainTile of them.
-// Separate from kTile, which the merge-path probes above share.
+// The chain kernel's own tile: ONE WAVE owns kChainTile seeds, as
+// kChainGroups groups of 256; in a group each lane owns kChainSeeds
+// CONSECUTIVE seeds (one dwordx4 per seed column).  Nothing is shared
+// between waves, so the kernel runs single-wave workgroups and needs no
+// hardware barrier.  Separate from kTile, which the merge-path probes above
+// share.
 constexpr int kChainSeeds = 4;
-constexpr int kChainTile = kChainSeeds * kBlock;
+constexpr int kChainWave = 64;
+constexpr int kChainGroups = 4;
+constexpr int kChainTile = kChainSeeds * kChainWave * kChainGroups;
 
 // per-(tile, src0-hop) windows: the seed region is subject-sorted, so the
 // B component is monotone — each kChainTile-seed tile's src-0 hop keys fall
@@ -1299,99 +1304,265 @@ __global__ void chain_tile_bounds(const int32_t* __restrict__ seed_b,
   }
 }
 
-// LDS staging: a tile's src-0 window (avg ~|region|/n_tiles rows) is probed
-// by all 256 threads of the block — stage it through LDS once and merge
-// there instead of hammering the same L1/L2 lines (guide: LDS-staged probe
-// structures).  At 16 KB + pad per block LDS never limits residency; the
-// kernel's registers do (6 blocks per CU as measured in round 3).
-constexpr int kChainLds = 4096;   // int32 rows a window may have to be staged
+// A tile's src-0 window holds exactly the region keys in [first, last], the
+// tile's first and last seed keys.  The wave answers the hop from its own
+// LDS slice of kChainSpan dwords, one of three ways (wave-uniform):
+//   direct count  last - first < kChainSpan: hist[key - first] += 1 per
+//                 window row (LDS atomic, no range check needed), then a
+//                 seed's count is hist[b - first] — no search at all, and
+//                 no row limit (rows beyond those loaded with the tile are
+//                 streamed);
+//   staged merge  the keys span more but the window has at most kChainSpan
+//                 rows: stage the rows and merge in LDS;
+//   global search anything else, and every window not above lds_min.
+// 8 KB + pad per wave: 16 resident waves per CU (what the registers allow)
+// take 129 of the 160 KB, so LDS does not lower residency.
+constexpr int kChainSpan = 2048;
+// partial sums the waves add their counts to, each on a 128-byte line of
+// its own; chain_total_kernel folds them
+constexpr int kChainParts = 256;
+constexpr int kChainPartStride = 16;
 // the 2 x b128 merge read may pass the window's end: the rows behind it
 // hold kChainPadKey, which no key compares above (a seed equal to it is
 // settled by the merge's search fallback)
 constexpr int kChainPad = 8;
 constexpr uint32_t kChainPadKey = 0xFFFFFFFFu;
-// window rows per thread that travel with the tile prefetch (in registers):
-// kChainPre * kBlock rows, one tile's worth when keys and seeds are 1:1;
-// the rest of a longer window is staged when the tile is processed
-constexpr int kChainPre = 4;
+// window rows per lane that are loaded with the tile's seeds (in registers):
+// kChainPre * kChainWave rows, one tile's worth when keys and seeds are
+// 1:1; the rest of a longer window is read when the tile is processed
+constexpr int kChainPre = kChainTile / kChainWave;
 
-// everything a tile needs from global memory before its search can start;
-// loaded one tile ahead so the loop waits for HBM once per block, not once
-// per tile
+enum ChainTier { kChainGlobal = 0, kChainMerge = 1, kChainDirect = 2 };
+
+// everything a tile needs from global memory before its LDS work can
+// start, loaded back to back
 struct ChainTileIn {
-  uint32_t b[kChainSeeds], z[kChainSeeds];
+  uint32_t b[kChainGroups][kChainSeeds], z[kChainGroups][kChainSeeds];
   uint32_t pw[kChainPre];
 };
 
-// one tile's window of one hop: block-uniform, so it lives in scalar
-// registers and can be fetched two tiles ahead for free
+// one tile's window of one hop and the tile's first and last valid seed
+// keys: wave-uniform, so they live in scalar registers
 struct ChainWin {
   int64_t lo, span;
+  uint32_t first, last;
 };
 
 __device__ __forceinline__ ChainWin chain_load_win(
-    const int64_t* __restrict__ win, int64_t t, int64_t m, int k, int h) {
-  ChainWin w{0, 0};
-  if (h >= 0 && t * kChainTile < m) {
+    const int64_t* __restrict__ win, int64_t t, int k, int h, uint32_t first,
+    uint32_t last) {
+  ChainWin w{0, 0, first, last};
+  if (h >= 0) {
     w.lo = win[(t * k + h) * 2];
     w.span = win[(t * k + h) * 2 + 1] - w.lo;
   }
   return w;
 }
 
-__device__ __forceinline__ bool chain_stages(int64_t wspan, int lds_min) {
-  return wspan > 0 && wspan <= kChainLds && wspan > lds_min;
+// `last - first`, not a span: that would wrap to 0 when the keys cover all
+// of u32.  The direct count holds a window row count in 32 bits.
+__device__ __forceinline__ int chain_tier(const ChainWin& w, int lds_min) {
+  if (w.span <= 0 || w.span <= lds_min) return kChainGlobal;
+  if (w.last - w.first < static_cast<uint32_t>(kChainSpan)
+      && w.span <= 0xFFFFFFFFll)
+    return kChainDirect;
+  return w.span <= kChainSpan ? kChainMerge : kChainGlobal;
 }
 
-// a thread's kChainSeeds consecutive seeds of one column.  `vec` is
-// block-uniform: a full tile behind a 16-byte aligned column pointer takes
+// one group's registers by a wave-uniform index.  Masks, not `?:` on the
+// arrays: that becomes a selected address and sends them to scratch.
+template <typename T>
+__device__ __forceinline__ void chain_pick(
+    const T (&a)[kChainGroups][kChainSeeds], int g, T (&out)[kChainSeeds]) {
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u) {
+    T v = 0;
+#pragma unroll
+    for (int j = 0; j < kChainGroups; ++j)
+      v |= a[j][u] & (g == j ? ~static_cast<T>(0) : static_cast<T>(0));
+    out[u] = v;
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void chain_put(
+    T (&a)[kChainGroups][kChainSeeds], int g, const T (&in)[kChainSeeds]) {
+#pragma unroll
+  for (int j = 0; j < kChainGroups; ++j) {
+    T take = g == j ? ~static_cast<T>(0) : static_cast<T>(0);
+#pragma unroll
+    for (int u = 0; u < kChainSeeds; ++u)
+      a[j][u] = (in[u] & take) | (a[j][u] & ~take);
+  }
+}
+
+// a lane's kChainSeeds consecutive seeds of one column.  `vec` is
+// wave-uniform: a full tile behind 16-byte aligned column pointers takes
 // one dwordx4; the tail tile and unaligned columns (a slice of a larger
-// tensor) take dword loads; seeds past the end read as 0 and their
-// contributions are dropped when the tile is summed.
+// tensor) take dword loads at a clamped index, nothing branching per seed;
+// seeds past the end read as 0 and their contributions are dropped when the
+// tile is summed.
+template <bool kVec>
 __device__ __forceinline__ void chain_load_seeds(
-    const int32_t* __restrict__ col, int64_t i0, int64_t m, bool vec,
+    const int32_t* __restrict__ col, int64_t i0, int64_t m,
     uint32_t (&out)[kChainSeeds]) {
-  if (vec) {
+  if (kVec) {
     uint4 v = *reinterpret_cast<const uint4*>(col + i0);
     out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
   } else {
 #pragma unroll
-    for (int u = 0; u < kChainSeeds; ++u)
-      out[u] = i0 + u < m ? static_cast<uint32_t>(col[i0 + u]) : 0u;
+    for (int u = 0; u < kChainSeeds; ++u) {
+      uint32_t v = static_cast<uint32_t>(col[min(i0 + u, m - 1)]);
+      out[u] = i0 + u < m ? v : 0u;
+    }
   }
 }
 
+// all seed and window loads of a tile, issued back to back
 __device__ __forceinline__ void chain_load_tile(
     ChainTileIn& in, int64_t t, const int32_t* __restrict__ seed_b,
     const int32_t* __restrict__ seed_z, int64_t m, const ChainHops& hops,
-    int hp, ChainWin w, bool b_vec, bool z_vec) {
-  int64_t i0 = t * kChainTile + threadIdx.x * kChainSeeds;
-  bool full = (t + 1) * kChainTile <= m;
-  chain_load_seeds(seed_b, i0, m, full && b_vec, in.b);
-  chain_load_seeds(seed_z, i0, m, full && z_vec, in.z);
+    int hp, const ChainWin& w, bool vec) {
+  if (__builtin_expect(vec && (t + 1) * kChainTile <= m, 1)) {
+#pragma unroll
+    for (int g = 0; g < kChainGroups; ++g) {
+      int64_t i0 = t * kChainTile
+          + (g * kChainWave + threadIdx.x) * kChainSeeds;
+      chain_load_seeds<true>(seed_b, i0, m, in.b[g]);
+      chain_load_seeds<true>(seed_z, i0, m, in.z[g]);
+    }
+  } else {
+#pragma unroll
+    for (int g = 0; g < kChainGroups; ++g) {
+      int64_t i0 = t * kChainTile
+          + (g * kChainWave + threadIdx.x) * kChainSeeds;
+      chain_load_seeds<false>(seed_b, i0, m, in.b[g]);
+      chain_load_seeds<false>(seed_z, i0, m, in.z[g]);
+    }
+  }
 #pragma unroll
   for (int j = 0; j < kChainPre; ++j) in.pw[j] = 0;
-  if (hp >= 0 && chain_stages(w.span, hops.lds_min)) {
-    // clamped, not predicated: no branch per row (rows past the window
-    // are replaced by the pad key when staged)
-    const int32_t* base = hops.key32[hp] + w.lo;
-    uint32_t n = static_cast<uint32_t>(w.span);
+  // the tier is known only once the seeds are here (it depends on their
+  // first and last key), so the rows are fetched for every window that may
+  // use the slice
+  if (hp >= 0 && w.span > 0 && w.span > hops.lds_min) {
+    const int32_t* base = hops.key32[hp] + w.lo + threadIdx.x;
+    if (__builtin_expect(w.span >= kChainTile, 1)) {
 #pragma unroll
-    for (int j = 0; j < kChainPre; ++j)
-      in.pw[j] = static_cast<uint32_t>(
-          base[min(threadIdx.x + j * kBlock, n - 1)]);
+      for (int j = 0; j < kChainPre; ++j)
+        in.pw[j] = static_cast<uint32_t>(base[j * kChainWave]);
+    } else {
+      // rows past the window stay 0: they are skipped or replaced by the
+      // pad key when the slice is filled
+      int n = static_cast<int>(w.span) - static_cast<int>(threadIdx.x);
+#pragma unroll
+      for (int j = 0; j < kChainPre; ++j)
+        if (j * kChainWave < n)
+          in.pw[j] = static_cast<uint32_t>(base[j * kChainWave]);
+    }
   }
 }
 
-// stage window rows [r0 + tid, n) from global memory and the pad behind them
+// the tile's first and last valid seed key, from the registers that hold
+// them (the keys chain_tile_bounds cut the windows by)
+__device__ __forceinline__ void chain_tile_keys(const ChainTileIn& in,
+                                                int64_t t, int64_t m,
+                                                ChainWin& w) {
+  int pos = static_cast<int>(
+      min((t + 1) * kChainTile, m) - 1 - t * kChainTile);
+  uint32_t at[kChainSeeds];
+  chain_pick(in.b, pos / (kChainWave * kChainSeeds), at);
+  uint32_t v = 0;
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u)
+    v |= at[u] & ((pos & (kChainSeeds - 1)) == u ? 0xFFFFFFFFu : 0u);
+  w.first = __builtin_amdgcn_readfirstlane(in.b[0][0]);
+  w.last = __builtin_amdgcn_readlane(
+      v, (pos / kChainSeeds) & (kChainWave - 1));
+}
+
+// The slice belongs to one wave, and a single-wave workgroup needs no
+// hardware barrier: this only orders the wave's own LDS accesses (lanes
+// read what other lanes wrote).
+__device__ __forceinline__ void chain_wave_sync() { __syncthreads(); }
+
+// stage window rows [r0 + lane, n) from global memory and the pad behind
+// them
 __device__ __forceinline__ void chain_stage_rows(
     uint32_t* lds, const int32_t* __restrict__ base, uint32_t n,
     uint32_t r0) {
-  for (uint32_t r = r0 + threadIdx.x; r < n + kChainPad; r += kBlock) {
+  for (uint32_t r = r0 + threadIdx.x; r < n + kChainPad; r += kChainWave) {
     uint32_t v = kChainPadKey;
     if (r < n) v = static_cast<uint32_t>(base[r]);
     lds[r] = v;
   }
+}
+
+// direct count: zero hist[0, nkeys) with b128 stores (the slice is a
+// multiple of 4 dwords, so rounding nkeys up stays inside it)
+__device__ __forceinline__ void chain_hist_zero(uint32_t* lds,
+                                                uint32_t nkeys) {
+  for (uint32_t i = threadIdx.x * 4; i < nkeys; i += kChainWave * 4)
+    *reinterpret_cast<uint4*>(lds + i) = make_uint4(0, 0, 0, 0);
+}
+
+__device__ __forceinline__ void chain_hist_add(uint32_t* lds, uint32_t key,
+                                               uint32_t first) {
+  __hip_atomic_fetch_add(&lds[key - first], 1u, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// direct count: window rows [r0 + lane, n) streamed from global memory.
+// Every row's key lies in [first, last], so no index is checked.
+__device__ __forceinline__ void chain_hist_rows(
+    uint32_t* lds, const int32_t* __restrict__ base, int64_t n, int64_t r0,
+    uint32_t first) {
+  for (int64_t r = r0 + threadIdx.x; r < n; r += kChainWave)
+    chain_hist_add(lds, static_cast<uint32_t>(base[r]), first);
+}
+
+// direct count: a seed's count is its key's bin.  A seed past the end
+// reads as 0: its index is clamped and its product dropped.
+__device__ __forceinline__ void chain_hist_read(
+    const uint32_t* lds, const uint32_t (&b)[kChainSeeds], uint32_t first,
+    uint32_t last, unsigned long long (&prod)[kChainSeeds]) {
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u)
+    prod[u] *= lds[min(b[u] - first, last - first)];
+}
+
+// fill the slice for one (tile, src-0 hop): the hop's histogram or its
+// staged rows.  `pw` are the window's first kChainPre * kChainWave rows if
+// they came with the tile's loads (pre), else everything is read here.
+__device__ __forceinline__ void chain_fill_slice(
+    uint32_t* lds, int tier, const int32_t* __restrict__ base,
+    const ChainWin& w, const uint32_t (&pw)[kChainPre], bool pre) {
+  uint32_t n = static_cast<uint32_t>(w.span);
+  if (tier == kChainDirect) {
+    chain_hist_zero(lds, w.last - w.first + 1);
+    chain_wave_sync();
+    if (pre && w.span >= kChainTile) {
+#pragma unroll
+      for (int j = 0; j < kChainPre; ++j) chain_hist_add(lds, pw[j], w.first);
+    } else if (pre) {
+#pragma unroll
+      for (int j = 0; j < kChainPre; ++j)
+        if (threadIdx.x + j * kChainWave < n)
+          chain_hist_add(lds, pw[j], w.first);
+    }
+    chain_hist_rows(lds, base, w.span, pre ? kChainPre * kChainWave : 0,
+                    w.first);
+  } else {
+    if (pre) {
+#pragma unroll
+      for (int j = 0; j < kChainPre; ++j) {
+        uint32_t r = threadIdx.x + j * kChainWave;
+        lds[r] = r < n ? pw[j] : kChainPadKey;
+      }
+    }
+    chain_stage_rows(lds, base, n, pre ? kChainPre * kChainWave : 0);
+  }
+  chain_wave_sync();
 }
 
 // lower bound over a staged window (n >= 1) by bit descent: the largest
@@ -1435,14 +1606,15 @@ __device__ __forceinline__ uint32_t chain_key(int32_t src, uint32_t b,
 // block-uniform branch around the seed loop, and the direct table takes a
 // clamped index (its range check is applied when the probe is finished)
 __device__ __forceinline__ void chain_probe_issue(
-    const ChainHops& hops, int h, const ChainTileIn& in,
+    const ChainHops& hops, int h, const uint32_t (&sb)[kChainSeeds],
+    const uint32_t (&sz)[kChainSeeds],
     uint32_t (&raw)[kChainSeeds]) {
   if (hops.direct[h] != nullptr) {
     // dense-value hop: counts[v - dmin], coalesced across the wave
 #pragma unroll
     for (int u = 0; u < kChainSeeds; ++u) {
       uint64_t off = static_cast<uint64_t>(
-          static_cast<int64_t>(chain_key(hops.src[h], in.b[u], in.z[u]))
+          static_cast<int64_t>(chain_key(hops.src[h], sb[u], sz[u]))
           - hops.dmin[h]);
       bool ok = off < static_cast<uint64_t>(hops.dlen[h]);
       raw[u] = hops.direct[h][ok ? off : 0];
@@ -1454,19 +1626,20 @@ __device__ __forceinline__ void chain_probe_issue(
 #pragma unroll
   for (int u = 0; u < kChainSeeds; ++u)
     raw[u] = hops.table32[h][
-        h32(chain_key(hops.src[h], in.b[u], in.z[u])) & mask];
+        h32(chain_key(hops.src[h], sb[u], sz[u])) & mask];
 }
 
 // multiply the hop's counts into prod; only a hash collision loads again
 __device__ __forceinline__ void chain_probe_finish(
-    const ChainHops& hops, int h, const ChainTileIn& in,
+    const ChainHops& hops, int h, const uint32_t (&sb)[kChainSeeds],
+    const uint32_t (&sz)[kChainSeeds],
     const uint32_t (&raw)[kChainSeeds],
     unsigned long long (&prod)[kChainSeeds]) {
   if (hops.direct[h] != nullptr) {
 #pragma unroll
     for (int u = 0; u < kChainSeeds; ++u) {
       uint64_t off = static_cast<uint64_t>(
-          static_cast<int64_t>(chain_key(hops.src[h], in.b[u], in.z[u]))
+          static_cast<int64_t>(chain_key(hops.src[h], sb[u], sz[u]))
           - hops.dmin[h]);
       prod[u] *= off < static_cast<uint64_t>(hops.dlen[h]) ? raw[u] : 0u;
     }
@@ -1475,7 +1648,7 @@ __device__ __forceinline__ void chain_probe_finish(
   uint32_t mask = static_cast<uint32_t>(hops.tmask[h]);
 #pragma unroll
   for (int u = 0; u < kChainSeeds; ++u) {
-    uint32_t v = chain_key(hops.src[h], in.b[u], in.z[u]);
+    uint32_t v = chain_key(hops.src[h], sb[u], sz[u]);
     uint32_t slot = h32(v) & mask;
     uint32_t e = raw[u];
     while (e != kTbl32Empty && (e >> 7) != v) {
@@ -1489,17 +1662,18 @@ __device__ __forceinline__ void chain_probe_finish(
 // u64 count-table hop: one 8-byte L2 load per seed (vs log2(n) lines),
 // the four first probes issued together
 __device__ __forceinline__ void chain_table64_hop(
-    const ChainHops& hops, int h, const ChainTileIn& in,
+    const ChainHops& hops, int h, const uint32_t (&sb)[kChainSeeds],
+    const uint32_t (&sz)[kChainSeeds],
     unsigned long long (&prod)[kChainSeeds]) {
   uint32_t mask = static_cast<uint32_t>(hops.tmask[h]);
   unsigned long long raw[kChainSeeds];
 #pragma unroll
   for (int u = 0; u < kChainSeeds; ++u)
     raw[u] = hops.table[h][
-        h32(chain_key(hops.src[h], in.b[u], in.z[u])) & mask];
+        h32(chain_key(hops.src[h], sb[u], sz[u])) & mask];
 #pragma unroll
   for (int u = 0; u < kChainSeeds; ++u) {
-    uint32_t v = chain_key(hops.src[h], in.b[u], in.z[u]);
+    uint32_t v = chain_key(hops.src[h], sb[u], sz[u]);
     uint32_t slot = h32(v) & mask;
     unsigned long long e = raw[u];
     while (e != kTblEmpty && static_cast<uint32_t>(e >> 32) != v) {
@@ -1548,10 +1722,12 @@ __device__ __forceinline__ void chain_merge_lds(
 // global memory.  Off the hot path; region sizes are int64 by contract.
 __device__ __forceinline__ void chain_global_hop(
     const int32_t* __restrict__ base, int64_t wspan, int32_t src,
-    const ChainTileIn& in, unsigned long long (&prod)[kChainSeeds]) {
+    const uint32_t (&sb)[kChainSeeds],
+    const uint32_t (&sz)[kChainSeeds],
+    unsigned long long (&prod)[kChainSeeds]) {
 #pragma unroll
   for (int u = 0; u < kChainSeeds; ++u) {
-    uint32_t key = chain_key(src, in.b[u], in.z[u]);
+    uint32_t key = chain_key(src, sb[u], sz[u]);
     int64_t lo = lower_bound_u32(base, wspan, key);
     // match runs are tiny (one object per subject in typical star data):
     // walk forward a few cache-hot slots instead of paying a second full
@@ -1566,125 +1742,259 @@ __device__ __forceinline__ void chain_global_hop(
   }
 }
 
-// Tiles are software-pipelined.  While tile i is staged and merged, tile
-// i+1's seeds and window rows are in flight (its window bounds were
-// fetched an iteration earlier still), and tile i's first table probe is
-// issued before that work and consumed after it, so a block waits for
-// global memory once, not once per tile.  There are no per-seed
-// predicates: seeds past the end read as 0 and their products are dropped
-// when the tile is summed.
-__global__ void __launch_bounds__(kBlock)
+// one src-0 search hop of one 256-seed group, answered from the wave's
+// slice (filled by chain_fill_slice) or, in the global tier, from memory
+__device__ __forceinline__ void chain_window_hop(
+    const uint32_t* lds, int tier, const int32_t* __restrict__ base,
+    const ChainWin& w, const uint32_t (&sb)[kChainSeeds],
+    const uint32_t (&sz)[kChainSeeds],
+    unsigned long long (&prod)[kChainSeeds]) {
+  if (tier == kChainDirect)
+    chain_hist_read(lds, sb, w.first, w.last, prod);
+  else if (tier == kChainMerge)
+    chain_merge_lds(lds, static_cast<uint32_t>(w.span), sb, prod);
+  else
+    chain_global_hop(base, w.span, 0, sb, sz, prod);
+}
+
+// every hop but the further src-0 window hops, for one 256-seed group,
+// multiplied into prod; products of seeds past the end come back as 0.
+// hp or ht < 0: no window hop here, no probe issued ahead.
+__device__ __forceinline__ void chain_group(
+    const uint32_t* lds, const ChainHops& hops, int hp, int ht, int tier,
+    const int32_t* __restrict__ base, const ChainWin& w,
+    const uint32_t (&sb)[kChainSeeds], const uint32_t (&sz)[kChainSeeds],
+    const uint32_t (&raw)[kChainSeeds], int64_t t, int g, int64_t m,
+    unsigned long long (&prod)[kChainSeeds]) {
+  if (hp >= 0) chain_window_hop(lds, tier, base, w, sb, sz, prod);
+  if (ht >= 0) chain_probe_finish(hops, ht, sb, sz, raw, prod);
+  for (int h = 0; h < hops.k; ++h) {
+    if (h == hp || h == ht) continue;
+    if (hops.table[h] != nullptr) {
+      chain_table64_hop(hops, h, sb, sz, prod);
+    } else if (chain_hop_is_probe32(hops, h)) {
+      uint32_t r2[kChainSeeds];
+      chain_probe_issue(hops, h, sb, sz, r2);
+      chain_probe_finish(hops, h, sb, sz, r2, prod);
+    } else if (hops.src[h] != 0) {
+      chain_global_hop(hops.key32[h], hops.n[h], hops.src[h], sb, sz, prod);
+    }
+  }
+  int64_t i0 = t * kChainTile + (g * kChainWave + threadIdx.x) * kChainSeeds;
+#pragma unroll
+  for (int u = 0; u < kChainSeeds; ++u)
+    prod[u] = i0 + u < m ? prod[u] : 0ull;
+}
+
+// One wave per workgroup and one tile at a time: the tile's loads go out
+// back to back, its first table probe is issued before the LDS work and
+// consumed after it, and what hides the memory latency is the other waves
+// of the CU, each on a tile of its own.  There are no per-seed predicates:
+// seeds past the end read as 0 and their products are dropped when the tile
+// is summed.
+__global__ void __launch_bounds__(kChainWave, 4)
 chain_count_kernel(const int32_t* __restrict__ seed_b,
                    const int32_t* __restrict__ seed_z, int64_t m,
                    ChainHops hops, const int64_t* __restrict__ win,
-                   unsigned long long* __restrict__ total) {
-  __shared__ __attribute__((aligned(16))) uint32_t lds[kChainLds + kChainPad];
+                   unsigned long long* __restrict__ parts, int n_parts) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kChainSpan + kChainPad];
   unsigned long long acc = 0;
-  // hp: the src-0 window hop whose rows travel with the tile prefetch;
-  // ht: the table hop whose first probe is issued ahead of the window work
+  // hp: the src-0 window hop whose rows are loaded with the tile's seeds;
+  // ht: the table hop whose first probe is issued ahead of the window work;
+  // more: there are further src-0 window hops, which reuse the slice once
+  // hp has been consumed
   int hp = -1, ht = -1;
+  bool more = false;
   for (int h = hops.k - 1; h >= 0; --h) {
-    if (chain_hop_is_probe32(hops, h)) ht = h;
-    else if (hops.table[h] == nullptr && hops.src[h] == 0) hp = h;
-  }
-  bool b_vec = (reinterpret_cast<uintptr_t>(seed_b) & 15) == 0;
-  bool z_vec = (reinterpret_cast<uintptr_t>(seed_z) & 15) == 0;
-  // block-uniform tile iteration (every thread of the block is in the same
-  // tile, and every staging decision reads block-uniform values) so the
-  // cooperative LDS loads can barrier safely
-  const int64_t step = gridDim.x;
-  int64_t t = blockIdx.x;
-  ChainTileIn cur = {}, nxt = {};
-  ChainWin w_cur = chain_load_win(win, t, m, hops.k, hp);
-  ChainWin w_nxt = chain_load_win(win, t + step, m, hops.k, hp);
-  if (t * kChainTile < m)
-    chain_load_tile(cur, t, seed_b, seed_z, m, hops, hp, w_cur, b_vec,
-                    z_vec);
-  for (; t * kChainTile < m; t += step) {
-    unsigned long long prod[kChainSeeds];
-    uint32_t raw[kChainSeeds];
-#pragma unroll
-    for (int u = 0; u < kChainSeeds; ++u) prod[u] = 1;
-    // the prefetched hop goes first: its rows leave the registers for LDS
-    // before the next tile's loads claim theirs, and before the table
-    // probe is issued, so that writing them waits for nothing newer
-    bool staged = hp >= 0 && chain_stages(w_cur.span, hops.lds_min);
-    uint32_t n_cur = static_cast<uint32_t>(w_cur.span);
-    if (staged) {
-#pragma unroll
-      for (int j = 0; j < kChainPre; ++j) {
-        uint32_t r = threadIdx.x + j * kBlock;
-        lds[r] = r < n_cur ? cur.pw[j] : kChainPadKey;
-      }
-      chain_stage_rows(lds, hops.key32[hp] + w_cur.lo, n_cur,
-                       kChainPre * kBlock);
+    if (chain_hop_is_probe32(hops, h)) {
+      ht = h;
+    } else if (hops.table[h] == nullptr && hops.src[h] == 0) {
+      more = hp >= 0;
+      hp = h;
     }
-    if (ht >= 0) chain_probe_issue(hops, ht, cur, raw);
-    if ((t + step) * kChainTile < m)
-      chain_load_tile(nxt, t + step, seed_b, seed_z, m, hops, hp, w_nxt,
-                      b_vec, z_vec);
-    ChainWin w_far = chain_load_win(win, t + 2 * step, m, hops.k, hp);
-    // hops in order, rotated so that the prefetched hop (already in LDS)
-    // comes first
-    for (int j = 0; j < hops.k; ++j) {
-      int h = j + max(hp, 0);
-      if (h >= hops.k) h -= hops.k;
-      if (h == ht) continue;
-      if (hops.table[h] != nullptr) {
-        chain_table64_hop(hops, h, cur, prod);
-        continue;
-      }
-      if (chain_hop_is_probe32(hops, h)) {
-        uint32_t r2[kChainSeeds];
-        chain_probe_issue(hops, h, cur, r2);
-        chain_probe_finish(hops, h, cur, r2, prod);
-        continue;
-      }
-      ChainWin w = h == hp ? w_cur : chain_load_win(win, t, m, hops.k, h);
-      const int32_t* base = hops.key32[h] + w.lo;
-      if (hops.src[h] == 0 && chain_stages(w.span, hops.lds_min)) {
-        // cooperative stage + barrier: merge in LDS, not HBM/L2
-        uint32_t n = static_cast<uint32_t>(w.span);
-        if (h != hp) chain_stage_rows(lds, base, n, 0);
-        __syncthreads();
-        chain_merge_lds(lds, n, cur.b, prod);
-        __syncthreads();  // before the next hop or tile reuses the buffer
-        continue;
-      }
-      chain_global_hop(base, w.span, hops.src[h], cur, prod);
-    }
-    if (ht >= 0) chain_probe_finish(hops, ht, cur, raw, prod);
-    int64_t i0 = t * kChainTile + threadIdx.x * kChainSeeds;
-#pragma unroll
-    for (int u = 0; u < kChainSeeds; ++u)
-      acc += i0 + u < m ? prod[u] : 0ull;
-    cur = nxt;
-    w_cur = w_nxt;
-    w_nxt = w_far;
   }
-  // wave reduction then one device-scope atomic per wave (guide G12)
+  // lean: no hop besides hp and ht
+  const bool lean = hops.k == (hp >= 0) + (ht >= 0);
+  const bool vec = ((reinterpret_cast<uintptr_t>(seed_b)
+                     | reinterpret_cast<uintptr_t>(seed_z)) & 15) == 0;
+  for (int64_t t = blockIdx.x; t * kChainTile < m; t += gridDim.x) {
+    ChainTileIn cur;
+    ChainWin w_cur = chain_load_win(win, t, hops.k, hp, 0, 0);
+    chain_load_tile(cur, t, seed_b, seed_z, m, hops, hp, w_cur, vec);
+    uint32_t raw[kChainGroups][kChainSeeds];
+    if (ht >= 0 && !more) {
+#pragma unroll
+      for (int g = 0; g < kChainGroups; ++g)
+        chain_probe_issue(hops, ht, cur.b[g], cur.z[g], raw[g]);
+    }
+    chain_tile_keys(cur, t, m, w_cur);
+    int tier = kChainGlobal;
+    const int32_t* base = nullptr;
+    if (hp >= 0) {
+      tier = chain_tier(w_cur, hops.lds_min);
+      base = hops.key32[hp] + w_cur.lo;
+      if (tier != kChainGlobal)
+        chain_fill_slice(lds, tier, base, w_cur, cur.pw, true);
+    }
+    if (__builtin_expect(lean && (hp < 0 || tier == kChainDirect), 1)) {
+      // the flagship's shape, fully unrolled: one bin read and one table
+      // probe per seed
+#pragma unroll
+      for (int g = 0; g < kChainGroups; ++g) {
+        unsigned long long prod[kChainSeeds];
+#pragma unroll
+        for (int u = 0; u < kChainSeeds; ++u) prod[u] = 1;
+        if (hp >= 0)
+          chain_hist_read(lds, cur.b[g], w_cur.first, w_cur.last, prod);
+        if (ht >= 0)
+          chain_probe_finish(hops, ht, cur.b[g], cur.z[g], raw[g], prod);
+        int64_t i0 = t * kChainTile
+            + (g * kChainWave + threadIdx.x) * kChainSeeds;
+#pragma unroll
+        for (int u = 0; u < kChainSeeds; ++u)
+          acc += i0 + u < m ? prod[u] : 0ull;
+      }
+    } else if (!more) {
+      // every other chain and tier: one copy of the code, the group's
+      // registers picked by index
+#pragma unroll 1
+      for (int g = 0; g < kChainGroups; ++g) {
+        uint32_t sb[kChainSeeds], sz[kChainSeeds], rw[kChainSeeds];
+        unsigned long long prod[kChainSeeds];
+        chain_pick(cur.b, g, sb);
+        chain_pick(cur.z, g, sz);
+        chain_pick(raw, g, rw);
+#pragma unroll
+        for (int u = 0; u < kChainSeeds; ++u) prod[u] = 1;
+        chain_group(lds, hops, hp, ht, tier, base, w_cur, sb, sz, rw, t, g,
+                    m, prod);
+#pragma unroll
+        for (int u = 0; u < kChainSeeds; ++u) acc += prod[u];
+      }
+    } else {
+      // further src-0 window hops reuse the slice once hp is consumed:
+      // the window hops go first, one after the other, their counts kept
+      // per seed, and every other hop follows (no probe was issued ahead:
+      // the kept products have its registers)
+      unsigned long long keep[kChainGroups][kChainSeeds];
+#pragma unroll
+      for (int g = 0; g < kChainGroups; ++g)
+#pragma unroll
+        for (int u = 0; u < kChainSeeds; ++u) keep[g][u] = 1;
+      for (int h = hp; h < hops.k; ++h) {
+        if (h == ht || hops.table[h] != nullptr
+            || chain_hop_is_probe32(hops, h) || hops.src[h] != 0)
+          continue;
+        ChainWin w = w_cur;
+        int tier_h = tier;
+        const int32_t* base_h = base;
+        if (h != hp) {
+          // this hop's rows did not come with the tile's loads
+          w = chain_load_win(win, t, hops.k, h, w_cur.first, w_cur.last);
+          tier_h = chain_tier(w, hops.lds_min);
+          base_h = hops.key32[h] + w.lo;
+          chain_wave_sync();  // the previous hop's reads are done
+          if (tier_h != kChainGlobal)
+            chain_fill_slice(lds, tier_h, base_h, w, cur.pw, false);
+        }
+#pragma unroll 1
+        for (int g = 0; g < kChainGroups; ++g) {
+          uint32_t sb[kChainSeeds], sz[kChainSeeds];
+          unsigned long long prod[kChainSeeds];
+          chain_pick(cur.b, g, sb);
+          chain_pick(cur.z, g, sz);
+          chain_pick(keep, g, prod);
+          chain_window_hop(lds, tier_h, base_h, w, sb, sz, prod);
+          chain_put(keep, g, prod);
+        }
+      }
+#pragma unroll 1
+      for (int g = 0; g < kChainGroups; ++g) {
+        uint32_t sb[kChainSeeds], sz[kChainSeeds];
+        unsigned long long prod[kChainSeeds];
+        chain_pick(cur.b, g, sb);
+        chain_pick(cur.z, g, sz);
+        chain_pick(keep, g, prod);
+        chain_group(lds, hops, -1, -1, kChainGlobal, nullptr, w_cur, sb, sz,
+                    sb, t, g, m, prod);
+#pragma unroll
+        for (int u = 0; u < kChainSeeds; ++u) acc += prod[u];
+      }
+    }
+    chain_wave_sync();  // before the next tile refills the slice
+  }
+  // wave reduction then one device-scope atomic per wave (guide G12), on
+  // one of n_parts partial sums: adds to ONE address are taken one after
+  // the other, about 11 ns each as measured, which for the 4096 waves of a
+  // full grid was half of the kernel
   for (int off = 32; off > 0; off >>= 1)
     acc += __shfl_down(acc, off);
-  if ((threadIdx.x & 63) == 0 && acc)
-    atomicAdd(total, acc);
+  if (threadIdx.x == 0 && acc)
+    atomicAdd(parts + (blockIdx.x % n_parts) * kChainPartStride, acc);
 }
 
-// One block per tile up to what the device keeps resident at once (asked of
-// the runtime, since it follows the kernel's register count); the rest
-// grid-stride, which is what the tile pipeline overlaps.  All blocks start
-// together, so none queues behind a full first round.
-inline int chain_grid(int64_t n_tiles) {
+// total = sum of the partial sums, which are left zeroed for the next query
+__global__ void __launch_bounds__(kChainParts)
+chain_total_kernel(unsigned long long* __restrict__ parts,
+                   unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long wave_sum[kChainParts / 64];
+  unsigned long long v = parts[threadIdx.x * kChainPartStride];
+  parts[threadIdx.x * kChainPartStride] = 0;
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x / 64] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int i = 0; i < kChainParts / 64; ++i) sum += wave_sum[i];
+    *total = sum;
+  }
+}
+
+// KOLIBRIE_CHAIN_GRID caps the chain kernel's grid in place of the default
+// below (0 or unset: the default), so that a small input can be made to
+// walk several tiles per wave, and a large one to take a wave per tile.
+inline int64_t chain_grid_cap() {
+  const char* e = getenv("KOLIBRIE_CHAIN_GRID");
+  return e ? std::max<int64_t>(0, atoll(e)) : 0;
+}
+
+// One wave per tile up to what the device keeps resident at once (asked of
+// the runtime, since it follows the kernel's registers and LDS); the rest
+// grid-stride.  All waves start together, so none queues behind a full
+// first round.  A wave per tile measured the same (round 4).
+inline int chain_grid(int64_t n_tiles, int64_t cap) {
   static const int resident = [] {
     int per_cu = 0, dev = 0, cus = 0;
     HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, chain_count_kernel, kBlock, 0));
+        &per_cu, chain_count_kernel, kChainWave, 0));
     HIP_OK(hipGetDevice(&dev));
     HIP_OK(hipDeviceGetAttribute(
         &cus, hipDeviceAttributeMultiprocessorCount, dev));
     return std::max(1, per_cu * cus);
   }();
-  return static_cast<int>(
-      std::max<int64_t>(1, std::min<int64_t>(n_tiles, resident)));
+  int64_t grid = std::min<int64_t>(n_tiles, cap > 0 ? cap : resident);
+  return static_cast<int>(std::max<int64_t>(1, grid));
+}
+
+// the chain kernel into `parts` (kChainParts zeroed partial sums) and their
+// sum into *total; with parts == nullptr every wave adds to *total itself
+// (a caller that brings no scratch), which must then be zero beforehand
+inline void chain_launch(const int32_t* seed_b, const int32_t* seed_z,
+                         int64_t m, const ChainHops& hops,
+                         const int64_t* win, unsigned long long* parts,
+                         unsigned long long* total, int64_t n_tiles,
+                         int64_t grid_cap, hipStream_t stream) {
+  hipLaunchKernelGGL(chain_count_kernel,
+                     dim3(chain_grid(n_tiles, grid_cap)), dim3(kChainWave),
+                     0, stream, seed_b, seed_z, m, hops, win,
+                     parts ? parts : total, parts ? kChainParts : 1);
+  HIP_OK(hipGetLastError());
+  if (parts) {
+    hipLaunchKernelGGL(chain_total_kernel, dim3(1), dim3(kChainParts), 0,
+                       stream, parts, total);
+    HIP_OK(hipGetLastError());
+  }
 }
 
 // Capture-friendly variant: caller owns the window + total buffers, no
@@ -1737,13 +2047,12 @@ void chain_count_into(at::Tensor seed_b, at::Tensor seed_z,
                      win.data_ptr<int64_t>(),
                      static_cast<unsigned long long*>(nullptr));
   HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(chain_count_kernel, dim3(chain_grid(n_tiles)),
-                     dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
-                     seed_z.data_ptr<int32_t>(), m, hops,
-                     win.data_ptr<int64_t>(),
-                     reinterpret_cast<unsigned long long*>(
-                         total.data_ptr<int64_t>()));
-  HIP_OK(hipGetLastError());
+  // the caller brings no scratch for partial sums
+  chain_launch(seed_b.data_ptr<int32_t>(), seed_z.data_ptr<int32_t>(), m,
+               hops, win.data_ptr<int64_t>(), nullptr,
+               reinterpret_cast<unsigned long long*>(
+                   total.data_ptr<int64_t>()),
+               n_tiles, chain_grid_cap(), stream);
 }
 
 // ---- C++ serving path (crush the per-query host
@@ -1757,7 +2066,7 @@ struct ChainServe {
   at::Tensor seed_b, seed_z, win, total;
   std::vector<at::Tensor> keep;
   ChainHops hops{};
-  int64_t m = 0, n_tiles = 0;
+  int64_t m = 0, n_tiles = 0, grid_cap = 0;
   int64_t* pinned = nullptr;
   ~ChainServe() {
     if (pinned) (void)hipHostFree(pinned);
@@ -1786,6 +2095,7 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
   cs->m = seed_b.numel();
   if (const char* e = getenv("KOLIBRIE_CHAIN_LDS_MIN"))
     cs->hops.lds_min = atoi(e);
+  cs->grid_cap = chain_grid_cap();
   cs->hops.k = static_cast<int>(hop_key32.size());
   for (size_t h = 0; h < hop_key32.size(); ++h) {
     TORCH_CHECK(hop_key32[h].dtype() == at::kInt);
@@ -1814,10 +2124,12 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
   cs->n_tiles = (cs->m + kChainTile - 1) / kChainTile;
   cs->win = at::empty({std::max<int64_t>(1, cs->n_tiles * cs->hops.k * 2)},
                       seed_b.options().dtype(at::kLong));
-  // total[0] = accumulator, total[1] = constant 1 (the completion flag's
+  // total[0] = the count, total[1] = constant 1 (the completion flag's
   // device source: same-stream copies are ordered, so once the flag
-  // lands in pinned memory the count before it is valid)
-  cs->total = at::zeros({2}, seed_b.options().dtype(at::kLong));
+  // lands in pinned memory the count before it is valid); behind them,
+  // from a 128-byte boundary, the partial sums
+  cs->total = at::zeros({kChainPartStride + kChainParts * kChainPartStride},
+                        seed_b.options().dtype(at::kLong));
   cs->total[1] = 1;
   HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&cs->pinned), 16));
   // the per-tile hop windows depend only on the CACHED seeds + hop
@@ -1845,18 +2157,16 @@ int64_t serve_chain_count(int64_t id) {
   int64_t* total_ptr = cs.total.data_ptr<int64_t>();
   volatile int64_t* flag = cs.pinned + 1;
   *flag = 0;
-  // windows were precomputed at registration; the accumulator was zeroed
-  // there (first call) or by the post-readback memset of the previous call
-  hipLaunchKernelGGL(chain_count_kernel, dim3(chain_grid(cs.n_tiles)),
-                     dim3(kBlock), 0, stream, cs.seed_b.data_ptr<int32_t>(),
-                     cs.seed_z.data_ptr<int32_t>(), cs.m, cs.hops,
-                     cs.win.data_ptr<int64_t>(),
-                     reinterpret_cast<unsigned long long*>(total_ptr));
+  // windows were precomputed at registration; the partial sums were zeroed
+  // there (first call) or by chain_total_kernel in the previous call
+  unsigned long long* total_u =
+      reinterpret_cast<unsigned long long*>(total_ptr);
+  chain_launch(cs.seed_b.data_ptr<int32_t>(), cs.seed_z.data_ptr<int32_t>(),
+               cs.m, cs.hops, cs.win.data_ptr<int64_t>(),
+               total_u + kChainPartStride, total_u, cs.n_tiles, cs.grid_cap,
+               stream);
   HIP_OK(hipMemcpyAsync(cs.pinned, total_ptr, 16, hipMemcpyDeviceToHost,
                         stream));
-  // re-zero for the NEXT call after the readback copy — off the
-  // critical path of this query's spin-wait
-  HIP_OK(hipMemsetAsync(total_ptr, 0, 8, stream));
   // spin on the pinned flag: hipStreamSynchronize pays tens of µs of
   // scheduler yield latency, the DMA lands in ~µs.  Bounded: fall back
   // to a real sync after ~2e9 spins (GPU hung elsewhere).
@@ -1930,13 +2240,15 @@ int64_t chain_count(at::Tensor seed_b, at::Tensor seed_z,
                        win.data_ptr<int64_t>(),
                        static_cast<unsigned long long*>(nullptr));
     HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(chain_count_kernel, dim3(chain_grid(n_tiles)),
-                       dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
-                       seed_z.data_ptr<int32_t>(), m, hops,
-                       win.data_ptr<int64_t>(),
-                       reinterpret_cast<unsigned long long*>(
-                           total.data_ptr<int64_t>()));
-    HIP_OK(hipGetLastError());
+    auto parts = at::zeros({kChainParts * kChainPartStride},
+                           seed_b.options().dtype(at::kLong));
+    chain_launch(seed_b.data_ptr<int32_t>(), seed_z.data_ptr<int32_t>(), m,
+                 hops, win.data_ptr<int64_t>(),
+                 reinterpret_cast<unsigned long long*>(
+                     parts.data_ptr<int64_t>()),
+                 reinterpret_cast<unsigned long long*>(
+                     total.data_ptr<int64_t>()),
+                 n_tiles, chain_grid_cap(), stream);
   }
   return total.item<int64_t>();
 }
@@ -4361,6 +4673,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K2 chained hash join over int32 key columns -> (li, ri)");
   m.def("chain_tile", []() { return static_cast<int64_t>(kChainTile); },
         "seed rows per chain tile (win buffer sizing)");
+  m.def("chain_span", []() { return static_cast<int64_t>(kChainSpan); },
+        "widest key span a tile's window is counted by direct address, and "
+        "the most window rows a tile stages for the LDS merge");
   m.def("chain_count", &chain_count,
         "fused COUNT(*) over a seed scan + probe-hop chain",
         py::arg("seed_b"), py::arg("seed_z"), py::arg("hop_key32"),
