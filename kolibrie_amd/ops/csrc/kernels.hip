@@ -78,135 +78,97 @@ __device__ __forceinline__ int64_t upper_bound_i64(const int64_t* __restrict__ a
 }
 
 // ---------------------------------------------------------------- K1: probe
-// exact mode: probe key = packed (a,b) per row; range mode: probe the full
-// range of leading component a (keys built from the int32 value).
-//
-__global__ void probe_count_exact(const int64_t* __restrict__ key12, int64_t n,
-                                  const int64_t* __restrict__ keys, int64_t m,
-                                  int64_t* __restrict__ lo_out,
-                                  int32_t* __restrict__ cnt_out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t k = keys[i];
-    int64_t lo = lower_bound_i64(key12, n, k);
-    int64_t hi = upper_bound_i64(key12, n, k);
-    lo_out[i] = lo;
-    cnt_out[i] = static_cast<int32_t>(hi - lo);
-  }
-}
+// Row i of a probe asks for the index rows whose packed key lies in
+// [lo(i), hi(i)].  The three key shapes differ only in how that pair is
+// formed; the count, tile-bounds and emit kernels are shared.
 
-__global__ void probe_count_range(const int64_t* __restrict__ key12, int64_t n,
-                                  const int32_t* __restrict__ vals, int64_t m,
-                                  int64_t* __restrict__ lo_out,
-                                  int32_t* __restrict__ cnt_out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t v = static_cast<int64_t>(vals[i]);
-    int64_t klo = (v << 32);                       // (v, 0x00000000)
-    int64_t khi = (v << 32) | 0xFFFFFFFFLL;        // (v, 0xFFFFFFFF)
-    int64_t lo = lower_bound_i64(key12, n, klo);
-    int64_t hi = upper_bound_i64(key12, n, khi);
-    lo_out[i] = lo;
-    cnt_out[i] = static_cast<int32_t>(hi - lo);
+// exact mode: probe key = packed (a,b) per row
+struct ExactKey {
+  const int64_t* keys;
+  __device__ __forceinline__ int64_t lo(int64_t i) const { return keys[i]; }
+  __device__ __forceinline__ int64_t hi(int64_t i) const { return keys[i]; }
+};
+
+// range mode: the full range of leading component a (keys built from the
+// int32 value)
+struct RangeKey {
+  const int32_t* vals;
+  __device__ __forceinline__ int64_t lo(int64_t i) const {
+    return static_cast<int64_t>(vals[i]) << 32;            // (v, 0x00000000)
   }
-}
+  __device__ __forceinline__ int64_t hi(int64_t i) const {
+    return (static_cast<int64_t>(vals[i]) << 32) | 0xFFFFFFFFLL;  // (v, ~0)
+  }
+};
+
+// fused mode: key (a<<32)|b packed inside the kernel, a/b each a per-row
+// column or a broadcast constant — the engine's bind-join step then needs
+// no separate pack2 pass
+struct FusedKey {
+  const int32_t* a_col;
+  int64_t a_const;
+  const int32_t* b_col;
+  int64_t b_const;
+  __device__ __forceinline__ int64_t lo(int64_t i) const {
+    int64_t a = a_col ? static_cast<int64_t>(a_col[i]) : a_const;
+    int64_t b = b_col ? static_cast<int64_t>(b_col[i]) : b_const;
+    return (a << 32) | (b & 0xFFFFFFFFLL);
+  }
+  __device__ __forceinline__ int64_t hi(int64_t i) const { return lo(i); }
+};
 
 // ---- merge-path variant for SORTED probes ---------------------------------
 // When the probe keys are themselves sorted (PSO-slice star/merge chains),
-// a fully-parallel boundary pass computes each 256-probe tile's index
+// a fully-parallel boundary pass computes each kTile-probe tile's index
 // window; the count pass then searches only inside its tile window, which
 // is small and cache-hot — the probe becomes a merge join.
 constexpr int kTile = 768;
+// fewer probes than this always take the unwindowed count
+constexpr int64_t kProbeSortedMin = 262144;
 
-__global__ void tile_bounds(const int64_t* __restrict__ key12, int64_t n,
-                            const int64_t* __restrict__ keys, int64_t m,
-                            int64_t n_tiles,
-                            int64_t* __restrict__ win_lo,
-                            int64_t* __restrict__ win_hi) {
+template <class Key>
+__global__ void probe_tile_bounds(const int64_t* __restrict__ key12, int64_t n,
+                                  Key key, int64_t m, int64_t n_tiles,
+                                  int64_t* __restrict__ win_lo,
+                                  int64_t* __restrict__ win_hi) {
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n_tiles;
        t += (int64_t)gridDim.x * blockDim.x) {
-    int64_t first = keys[t * kTile];
-    int64_t last = keys[min((t + 1) * kTile - 1, m - 1)];
+    int64_t first = key.lo(t * kTile);
+    int64_t last = key.hi(min((t + 1) * kTile - 1, m - 1));
     win_lo[t] = lower_bound_i64(key12, n, first);
     win_hi[t] = upper_bound_i64(key12, n, last);
   }
 }
 
-__global__ void probe_count_exact_sorted(const int64_t* __restrict__ key12,
-                                         const int64_t* __restrict__ keys,
-                                         int64_t m,
-                                         const int64_t* __restrict__ win_lo,
-                                         const int64_t* __restrict__ win_hi,
-                                         int64_t* __restrict__ lo_out,
-                                         int32_t* __restrict__ cnt_out) {
+// count: each probe row finds its [lo, lo+cnt) index range; kWindowed
+// confines the search to the row's tile window (win_lo/win_hi unused
+// otherwise)
+template <class Key, bool kWindowed>
+__global__ void probe_count(const int64_t* __restrict__ key12, int64_t n,
+                            Key key, int64_t m,
+                            const int64_t* __restrict__ win_lo,
+                            const int64_t* __restrict__ win_hi,
+                            int64_t* __restrict__ lo_out,
+                            int32_t* __restrict__ cnt_out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
        i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t t = i / kTile;
-    int64_t wlo = win_lo[t];
-    int64_t wspan = win_hi[t] - wlo;
-    int64_t k = keys[i];
-    int64_t lo = wlo + lower_bound_i64(key12 + wlo, wspan, k);
-    int64_t hi = wlo + upper_bound_i64(key12 + wlo, wspan, k);
+    int64_t wlo = 0, wspan = n;
+    if (kWindowed) {
+      int64_t t = i / kTile;
+      wlo = win_lo[t];
+      wspan = win_hi[t] - wlo;
+    }
+    int64_t klo = key.lo(i);
+    int64_t khi = key.hi(i);
+    int64_t lo = wlo + lower_bound_i64(key12 + wlo, wspan, klo);
+    int64_t hi = wlo + upper_bound_i64(key12 + wlo, wspan, khi);
     lo_out[i] = lo;
     cnt_out[i] = static_cast<int32_t>(hi - lo);
   }
 }
 
-// emit: each probe row copies its [lo, lo+cnt) range; writes probe-row index,
-// the second packed component (b) and the trailing column (z).
-__global__ void probe_emit(const int64_t* __restrict__ key12,
-                           const int32_t* __restrict__ z, int64_t m,
-                           const int64_t* __restrict__ lo,
-                           const int32_t* __restrict__ cnt,
-                           const int64_t* __restrict__ offs,
-                           int64_t* __restrict__ li_out,
-                           int32_t* __restrict__ b_out,
-                           int32_t* __restrict__ z_out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t base = offs[i];
-    int64_t l = lo[i];
-    int32_t c = cnt[i];
-    for (int32_t j = 0; j < c; ++j) {
-      li_out[base + j] = i;
-      b_out[base + j] = static_cast<int32_t>(key12[l + j] & 0xFFFFFFFFLL);
-      z_out[base + j] = z[l + j];
-    }
-  }
-}
-
-// balanced emit: parallel over OUTPUT elements (skew-proof — a probe row
-// with 10^4 matches no longer serializes one thread); each output finds its
-// probe row by binary search over the offset array.
-__global__ void probe_emit_balanced(const int64_t* __restrict__ key12,
-                                    const int32_t* __restrict__ z, int64_t m,
-                                    const int64_t* __restrict__ lo,
-                                    const int64_t* __restrict__ offs,  // [m+1]
-                                    int64_t total,
-                                    int64_t* __restrict__ li_out,
-                                    int32_t* __restrict__ b_out,
-                                    int32_t* __restrict__ z_out) {
-  for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-       idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-    // find probe row i with offs[i] <= idx < offs[i+1]
-    int64_t a = 0, b = m;
-    while (a + 1 < b) {
-      int64_t mid = (a + b) >> 1;
-      if (offs[mid] <= idx) a = mid; else b = mid;
-    }
-    int64_t j = idx - offs[a];
-    int64_t src = lo[a] + j;
-    li_out[idx] = a;
-    b_out[idx] = static_cast<int32_t>(key12[src] & 0xFFFFFFFFLL);
-    z_out[idx] = z[src];
-  }
-}
-
-// ---- fused probe: inline key packing + carry-column emit ------------------
-// Builds probe keys (a<<32)|b inside the kernel (a/b each a per-row column
-// or a broadcast constant) and gathers up to 4 "carry" columns by probe-row
-// index during the emit pass — the engine's bind-join step then needs no
-// separate pack2 pass and no separate gathers.
+// up to 4 "carry" columns are gathered by probe-row index during the emit
+// pass, so the engine needs no separate gathers; k == 0 carries nothing
 constexpr int kMaxCarry = 4;
 
 struct CarryCols {
@@ -215,77 +177,18 @@ struct CarryCols {
   int k;
 };
 
-__device__ __forceinline__ int64_t fused_key(const int32_t* a_col, int64_t a_const,
-                                             const int32_t* b_col, int64_t b_const,
-                                             int64_t i) {
-  int64_t a = a_col ? static_cast<int64_t>(a_col[i]) : a_const;
-  int64_t b = b_col ? static_cast<int64_t>(b_col[i]) : b_const;
-  return (a << 32) | (b & 0xFFFFFFFFLL);
-}
-
-__global__ void probe_count_fused(const int64_t* __restrict__ key12, int64_t n,
-                                  const int32_t* __restrict__ a_col, int64_t a_const,
-                                  const int32_t* __restrict__ b_col, int64_t b_const,
-                                  int64_t m,
-                                  int64_t* __restrict__ lo_out,
-                                  int32_t* __restrict__ cnt_out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t k = fused_key(a_col, a_const, b_col, b_const, i);
-    int64_t lo = lower_bound_i64(key12, n, k);
-    int64_t hi = upper_bound_i64(key12, n, k);
-    lo_out[i] = lo;
-    cnt_out[i] = static_cast<int32_t>(hi - lo);
-  }
-}
-
-__global__ void tile_bounds_fused(const int64_t* __restrict__ key12, int64_t n,
-                                  const int32_t* __restrict__ a_col, int64_t a_const,
-                                  const int32_t* __restrict__ b_col, int64_t b_const,
-                                  int64_t m, int64_t n_tiles,
-                                  int64_t* __restrict__ win_lo,
-                                  int64_t* __restrict__ win_hi) {
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n_tiles;
-       t += (int64_t)gridDim.x * blockDim.x) {
-    int64_t first = fused_key(a_col, a_const, b_col, b_const, t * kTile);
-    int64_t last = fused_key(a_col, a_const, b_col, b_const,
-                             min((t + 1) * kTile - 1, m - 1));
-    win_lo[t] = lower_bound_i64(key12, n, first);
-    win_hi[t] = upper_bound_i64(key12, n, last);
-  }
-}
-
-__global__ void probe_count_fused_sorted(const int64_t* __restrict__ key12,
-                                         const int32_t* __restrict__ a_col, int64_t a_const,
-                                         const int32_t* __restrict__ b_col, int64_t b_const,
-                                         int64_t m,
-                                         const int64_t* __restrict__ win_lo,
-                                         const int64_t* __restrict__ win_hi,
-                                         int64_t* __restrict__ lo_out,
-                                         int32_t* __restrict__ cnt_out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t t = i / kTile;
-    int64_t wlo = win_lo[t];
-    int64_t wspan = win_hi[t] - wlo;
-    int64_t k = fused_key(a_col, a_const, b_col, b_const, i);
-    int64_t lo = wlo + lower_bound_i64(key12 + wlo, wspan, k);
-    int64_t hi = wlo + upper_bound_i64(key12 + wlo, wspan, k);
-    lo_out[i] = lo;
-    cnt_out[i] = static_cast<int32_t>(hi - lo);
-  }
-}
-
-__global__ void probe_emit_carry(const int64_t* __restrict__ key12,
-                                 const int32_t* __restrict__ z, int64_t m,
-                                 const int64_t* __restrict__ lo,
-                                 const int32_t* __restrict__ cnt,
-                                 const int64_t* __restrict__ offs,
-                                 CarryCols carry,
-                                 int64_t* __restrict__ li_out,
-                                 int32_t* __restrict__ b_out,
-                                 int32_t* __restrict__ z_out,
-                                 bool emit_b) {
+// emit: each probe row copies its [lo, lo+cnt) range; writes probe-row index,
+// the second packed component (b, when emit_b) and the trailing column (z).
+__global__ void probe_emit(const int64_t* __restrict__ key12,
+                           const int32_t* __restrict__ z, int64_t m,
+                           const int64_t* __restrict__ lo,
+                           const int32_t* __restrict__ cnt,
+                           const int64_t* __restrict__ offs,
+                           CarryCols carry,
+                           int64_t* __restrict__ li_out,
+                           int32_t* __restrict__ b_out,
+                           int32_t* __restrict__ z_out,
+                           bool emit_b) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
        i += (int64_t)gridDim.x * blockDim.x) {
     int64_t base = offs[i];
@@ -303,17 +206,21 @@ __global__ void probe_emit_carry(const int64_t* __restrict__ key12,
   }
 }
 
-__global__ void probe_emit_carry_balanced(const int64_t* __restrict__ key12,
-                                          const int32_t* __restrict__ z, int64_t m,
-                                          const int64_t* __restrict__ lo,
-                                          const int64_t* __restrict__ offs,  // [m+1]
-                                          int64_t total, CarryCols carry,
-                                          int64_t* __restrict__ li_out,
-                                          int32_t* __restrict__ b_out,
-                                          int32_t* __restrict__ z_out,
-                                          bool emit_b) {
+// balanced emit: parallel over OUTPUT elements (skew-proof — a probe row
+// with 10^4 matches no longer serializes one thread); each output finds its
+// probe row by binary search over the offset array.
+__global__ void probe_emit_balanced(const int64_t* __restrict__ key12,
+                                    const int32_t* __restrict__ z, int64_t m,
+                                    const int64_t* __restrict__ lo,
+                                    const int64_t* __restrict__ offs,  // [m+1]
+                                    int64_t total, CarryCols carry,
+                                    int64_t* __restrict__ li_out,
+                                    int32_t* __restrict__ b_out,
+                                    int32_t* __restrict__ z_out,
+                                    bool emit_b) {
   for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
        idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    // find probe row a with offs[a] <= idx < offs[a+1]
     int64_t a = 0, b = m;
     while (a + 1 < b) {
       int64_t mid = (a + b) >> 1;
@@ -388,14 +295,15 @@ __device__ __forceinline__ void hj_lds_build(KeyCols build, int64_t r,
   __syncthreads();
 }
 
-__global__ void hj_count_lds(KeyCols probe, int64_t l, KeyCols build,
-                             int64_t r, int32_t* __restrict__ cnt) {
-  __shared__ int32_t heads[kHjLdsSlots];
-  __shared__ int32_t next[kHjLdsRows];
-  hj_lds_build(build, r, heads, next);
+// The chain walks of the count and emit passes, over a table in either
+// memory; forced inline so that each caller's address space is known.
+__device__ __forceinline__ void hj_count_rows(
+    const KeyCols& probe, int64_t l, const KeyCols& build,
+    const int32_t* heads, const int32_t* next, uint32_t mask,
+    int32_t* __restrict__ cnt) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < l;
        i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & (kHjLdsSlots - 1);
+    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & mask;
     int32_t c = 0;
     for (int32_t b = heads[h]; b >= 0; b = next[b])
       if (keys_equal(probe, i, build, b)) ++c;
@@ -403,16 +311,14 @@ __global__ void hj_count_lds(KeyCols probe, int64_t l, KeyCols build,
   }
 }
 
-__global__ void hj_emit_lds(KeyCols probe, int64_t l, KeyCols build,
-                            int64_t r, const int64_t* __restrict__ offs,
-                            int64_t* __restrict__ li_out,
-                            int64_t* __restrict__ ri_out) {
-  __shared__ int32_t heads[kHjLdsSlots];
-  __shared__ int32_t next[kHjLdsRows];
-  hj_lds_build(build, r, heads, next);
+__device__ __forceinline__ void hj_emit_rows(
+    const KeyCols& probe, int64_t l, const KeyCols& build,
+    const int32_t* heads, const int32_t* next, uint32_t mask,
+    const int64_t* __restrict__ offs, int64_t* __restrict__ li_out,
+    int64_t* __restrict__ ri_out) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < l;
        i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & (kHjLdsSlots - 1);
+    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & mask;
     int64_t base = offs[i];
     for (int32_t b = heads[h]; b >= 0; b = next[b]) {
       if (keys_equal(probe, i, build, b)) {
@@ -424,37 +330,38 @@ __global__ void hj_emit_lds(KeyCols probe, int64_t l, KeyCols build,
   }
 }
 
-__global__ void hj_count(KeyCols probe, int64_t l, KeyCols build,
+// kLds: every block stages the table in LDS and ignores heads/next/mask;
+// otherwise they are the global table that hj_build filled.
+template <bool kLds>
+__global__ void hj_count(KeyCols probe, int64_t l, KeyCols build, int64_t r,
                          const int32_t* __restrict__ heads,
                          const int32_t* __restrict__ next, uint32_t mask,
                          int32_t* __restrict__ cnt) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < l;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & mask;
-    int32_t c = 0;
-    for (int32_t r = heads[h]; r >= 0; r = next[r])
-      if (keys_equal(probe, i, build, r)) ++c;
-    cnt[i] = c;
+  if constexpr (kLds) {
+    __shared__ int32_t lds_heads[kHjLdsSlots];
+    __shared__ int32_t lds_next[kHjLdsRows];
+    hj_lds_build(build, r, lds_heads, lds_next);
+    hj_count_rows(probe, l, build, lds_heads, lds_next, kHjLdsSlots - 1, cnt);
+  } else {
+    hj_count_rows(probe, l, build, heads, next, mask, cnt);
   }
 }
 
-__global__ void hj_emit(KeyCols probe, int64_t l, KeyCols build,
+template <bool kLds>
+__global__ void hj_emit(KeyCols probe, int64_t l, KeyCols build, int64_t r,
                         const int32_t* __restrict__ heads,
                         const int32_t* __restrict__ next, uint32_t mask,
                         const int64_t* __restrict__ offs,
                         int64_t* __restrict__ li_out,
                         int64_t* __restrict__ ri_out) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < l;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & mask;
-    int64_t base = offs[i];
-    for (int32_t r = heads[h]; r >= 0; r = next[r]) {
-      if (keys_equal(probe, i, build, r)) {
-        li_out[base] = i;
-        ri_out[base] = r;
-        ++base;
-      }
-    }
+  if constexpr (kLds) {
+    __shared__ int32_t lds_heads[kHjLdsSlots];
+    __shared__ int32_t lds_next[kHjLdsRows];
+    hj_lds_build(build, r, lds_heads, lds_next);
+    hj_emit_rows(probe, l, build, lds_heads, lds_next, kHjLdsSlots - 1, offs,
+                 li_out, ri_out);
+  } else {
+    hj_emit_rows(probe, l, build, heads, next, mask, offs, li_out, ri_out);
   }
 }
 
@@ -1997,6 +1904,69 @@ inline void chain_launch(const int32_t* seed_b, const int32_t* seed_z,
   }
 }
 
+// The hop lists of every chain entry point -> ChainHops.  All checks come
+// before the first write: the struct's arrays hold kMaxHops entries.
+static ChainHops chain_hops_from(const std::vector<at::Tensor>& hop_key32,
+                                 const std::vector<int64_t>& hop_src,
+                                 const std::vector<at::Tensor>& hop_table,
+                                 const std::vector<int64_t>& hop_dmin) {
+  const size_t k = hop_key32.size();
+  TORCH_CHECK(k <= static_cast<size_t>(kMaxHops), "chain: at most ",
+              kMaxHops, " hops, got ", k);
+  TORCH_CHECK(hop_src.size() == k && hop_table.size() == k,
+              "chain: hop_key32, hop_src and hop_table differ in length");
+  TORCH_CHECK(hop_dmin.size() <= k, "chain: hop_dmin longer than the hops");
+  auto is_direct = [&](size_t h) {
+    return h < hop_dmin.size() && hop_dmin[h] >= 0;
+  };
+  for (size_t h = 0; h < k; ++h) {
+    TORCH_CHECK(hop_key32[h].is_cuda() && hop_key32[h].dtype() == at::kInt,
+                "chain: hop_key32 must be int32 on the device");
+    if (hop_table[h].numel() == 0) continue;
+    TORCH_CHECK(hop_table[h].is_cuda()
+                && (hop_table[h].dtype() == at::kLong
+                    || hop_table[h].dtype() == at::kInt),
+                "chain: hop_table must be int32 or int64 on the device");
+    TORCH_CHECK(!is_direct(h) || hop_table[h].dtype() == at::kInt,
+                "chain: a direct-indexed hop_table must be int32");
+  }
+  ChainHops hops{};
+  if (const char* e = getenv("KOLIBRIE_CHAIN_LDS_MIN"))
+    hops.lds_min = atoi(e);
+  hops.k = static_cast<int>(k);
+  for (size_t h = 0; h < k; ++h) {
+    hops.key32[h] = hop_key32[h].data_ptr<int32_t>();
+    hops.n[h] = hop_key32[h].numel();
+    hops.src[h] = static_cast<int32_t>(hop_src[h]);
+    if (hop_table[h].numel() == 0) continue;
+    if (is_direct(h)) {
+      hops.direct[h] = reinterpret_cast<const uint32_t*>(
+          hop_table[h].data_ptr<int32_t>());
+      hops.dmin[h] = hop_dmin[h];
+      hops.dlen[h] = hop_table[h].numel();
+    } else if (hop_table[h].dtype() == at::kInt) {
+      hops.table32[h] = reinterpret_cast<const uint32_t*>(
+          hop_table[h].data_ptr<int32_t>());
+    } else {
+      hops.table[h] = reinterpret_cast<const unsigned long long*>(
+          hop_table[h].data_ptr<int64_t>());
+    }
+    hops.tmask[h] = hop_table[h].numel() - 1;
+  }
+  return hops;
+}
+
+// per-tile hop windows into `win`; a non-null `zero` has its partial sums
+// cleared by the same launch
+inline void chain_bounds_launch(const int32_t* seed_b, int64_t m,
+                                int64_t n_tiles, const ChainHops& hops,
+                                int64_t* win, unsigned long long* zero,
+                                hipStream_t stream) {
+  hipLaunchKernelGGL(chain_tile_bounds, dim3(grid_for(n_tiles)), dim3(kBlock),
+                     0, stream, seed_b, m, n_tiles, hops, win, zero);
+  HIP_OK(hipGetLastError());
+}
+
 // Capture-friendly variant: caller owns the window + total buffers, no
 // allocation and no device->host sync inside — the launch pair can be
 // recorded into a hipGraph and replayed per query (launch-bound path).
@@ -2010,43 +1980,14 @@ void chain_count_into(at::Tensor seed_b, at::Tensor seed_z,
               && seed_z.is_cuda());
   TORCH_CHECK(win.dtype() == at::kLong && total.dtype() == at::kLong);
   int64_t m = seed_b.numel();
-  ChainHops hops{};
-  if (const char* e = getenv("KOLIBRIE_CHAIN_LDS_MIN"))
-    hops.lds_min = atoi(e);
-  hops.k = static_cast<int>(hop_key32.size());
-  for (size_t h = 0; h < hop_key32.size(); ++h) {
-    TORCH_CHECK(hop_key32[h].dtype() == at::kInt);
-    hops.key32[h] = hop_key32[h].data_ptr<int32_t>();
-    hops.n[h] = hop_key32[h].numel();
-    hops.src[h] = static_cast<int32_t>(hop_src[h]);
-    if (hop_table[h].numel() > 0) {
-      bool is_direct = h < hop_dmin.size() && hop_dmin[h] >= 0;
-      if (is_direct) {
-        hops.direct[h] = reinterpret_cast<const uint32_t*>(
-            hop_table[h].data_ptr<int32_t>());
-        hops.dmin[h] = hop_dmin[h];
-        hops.dlen[h] = hop_table[h].numel();
-      } else if (hop_table[h].dtype() == at::kInt) {
-        hops.table32[h] = reinterpret_cast<const uint32_t*>(
-            hop_table[h].data_ptr<int32_t>());
-      } else {
-        hops.table[h] = reinterpret_cast<const unsigned long long*>(
-            hop_table[h].data_ptr<int64_t>());
-      }
-      hops.tmask[h] = hop_table[h].numel() - 1;
-    }
-  }
+  ChainHops hops = chain_hops_from(hop_key32, hop_src, hop_table, hop_dmin);
   auto stream = cur_stream();
   total.zero_();
   if (m == 0) return;
   int64_t n_tiles = (m + kChainTile - 1) / kChainTile;
   TORCH_CHECK(win.numel() >= n_tiles * hops.k * 2, "win buffer too small");
-  hipLaunchKernelGGL(chain_tile_bounds, dim3(grid_for(n_tiles)),
-                     dim3(kBlock), 0, stream,
-                     seed_b.data_ptr<int32_t>(), m, n_tiles, hops,
-                     win.data_ptr<int64_t>(),
-                     static_cast<unsigned long long*>(nullptr));
-  HIP_OK(hipGetLastError());
+  chain_bounds_launch(seed_b.data_ptr<int32_t>(), m, n_tiles, hops,
+                      win.data_ptr<int64_t>(), nullptr, stream);
   // the caller brings no scratch for partial sums
   chain_launch(seed_b.data_ptr<int32_t>(), seed_z.data_ptr<int32_t>(), m,
                hops, win.data_ptr<int64_t>(), nullptr,
@@ -2082,6 +2023,7 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
   TORCH_CHECK(seed_b.is_cuda() && seed_b.dtype() == at::kInt
               && seed_z.is_cuda());
   auto cs = std::make_unique<ChainServe>();
+  cs->hops = chain_hops_from(hop_key32, hop_src, hop_table, hop_dmin);
   // the kernel reads each seed column with dwordx4 when its pointer is
   // 16-byte aligned; seed_z usually arrives as a slice of the PSO column,
   // aligned to 4 bytes only.  The seeds are immutable for this
@@ -2093,34 +2035,10 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
   cs->seed_b = aligned16(seed_b);
   cs->seed_z = aligned16(seed_z);
   cs->m = seed_b.numel();
-  if (const char* e = getenv("KOLIBRIE_CHAIN_LDS_MIN"))
-    cs->hops.lds_min = atoi(e);
   cs->grid_cap = chain_grid_cap();
-  cs->hops.k = static_cast<int>(hop_key32.size());
-  for (size_t h = 0; h < hop_key32.size(); ++h) {
-    TORCH_CHECK(hop_key32[h].dtype() == at::kInt);
-    cs->keep.push_back(hop_key32[h]);
-    cs->keep.push_back(hop_table[h]);
-    cs->hops.key32[h] = hop_key32[h].data_ptr<int32_t>();
-    cs->hops.n[h] = hop_key32[h].numel();
-    cs->hops.src[h] = static_cast<int32_t>(hop_src[h]);
-    if (hop_table[h].numel() > 0) {
-      bool is_direct = h < hop_dmin.size() && hop_dmin[h] >= 0;
-      if (is_direct) {
-        cs->hops.direct[h] = reinterpret_cast<const uint32_t*>(
-            hop_table[h].data_ptr<int32_t>());
-        cs->hops.dmin[h] = hop_dmin[h];
-        cs->hops.dlen[h] = hop_table[h].numel();
-      } else if (hop_table[h].dtype() == at::kInt) {
-        cs->hops.table32[h] = reinterpret_cast<const uint32_t*>(
-            hop_table[h].data_ptr<int32_t>());
-      } else {
-        cs->hops.table[h] = reinterpret_cast<const unsigned long long*>(
-            hop_table[h].data_ptr<int64_t>());
-      }
-      cs->hops.tmask[h] = hop_table[h].numel() - 1;
-    }
-  }
+  // the hops point into these tensors
+  cs->keep = hop_key32;
+  cs->keep.insert(cs->keep.end(), hop_table.begin(), hop_table.end());
   cs->n_tiles = (cs->m + kChainTile - 1) / kChainTile;
   cs->win = at::empty({std::max<int64_t>(1, cs->n_tiles * cs->hops.k * 2)},
                       seed_b.options().dtype(at::kLong));
@@ -2138,13 +2056,11 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
   // chain_tile_bounds was ~8% of the serve step.  It also zeroes the
   // accumulator, so the first serve call starts clean.
   if (cs->m > 0) {
-    hipLaunchKernelGGL(chain_tile_bounds, dim3(grid_for(cs->n_tiles)),
-                       dim3(kBlock), 0, cur_stream(),
-                       cs->seed_b.data_ptr<int32_t>(), cs->m, cs->n_tiles,
-                       cs->hops, cs->win.data_ptr<int64_t>(),
-                       reinterpret_cast<unsigned long long*>(
-                           cs->total.data_ptr<int64_t>()));
-    HIP_OK(hipGetLastError());
+    chain_bounds_launch(cs->seed_b.data_ptr<int32_t>(), cs->m, cs->n_tiles,
+                        cs->hops, cs->win.data_ptr<int64_t>(),
+                        reinterpret_cast<unsigned long long*>(
+                            cs->total.data_ptr<int64_t>()),
+                        cur_stream());
   }
   g_chain_serves.push_back(std::move(cs));
   return static_cast<int64_t>(g_chain_serves.size() - 1);
@@ -2194,52 +2110,16 @@ int64_t chain_count(at::Tensor seed_b, at::Tensor seed_z,
                     std::vector<int64_t> hop_dmin) {
   TORCH_CHECK(seed_b.is_cuda() && seed_b.dtype() == at::kInt
               && seed_z.is_cuda());
-  TORCH_CHECK(hop_key32.size() <= static_cast<size_t>(kMaxHops));
-  TORCH_CHECK(hop_key32.size() == hop_src.size()
-              && hop_key32.size() == hop_table.size());
   int64_t m = seed_b.numel();
-  ChainHops hops{};
-  if (const char* e = getenv("KOLIBRIE_CHAIN_LDS_MIN"))
-    hops.lds_min = atoi(e);
-  hops.k = static_cast<int>(hop_key32.size());
-  for (size_t h = 0; h < hop_key32.size(); ++h) {
-    TORCH_CHECK(hop_key32[h].is_cuda() && hop_key32[h].dtype() == at::kInt);
-    hops.key32[h] = hop_key32[h].data_ptr<int32_t>();
-    hops.n[h] = hop_key32[h].numel();
-    hops.src[h] = static_cast<int32_t>(hop_src[h]);
-    if (hop_table[h].numel() > 0) {
-      TORCH_CHECK(hop_table[h].is_cuda()
-                  && (hop_table[h].dtype() == at::kLong
-                      || hop_table[h].dtype() == at::kInt));
-      bool is_direct = h < hop_dmin.size() && hop_dmin[h] >= 0;
-      if (is_direct) {
-        hops.direct[h] = reinterpret_cast<const uint32_t*>(
-            hop_table[h].data_ptr<int32_t>());
-        hops.dmin[h] = hop_dmin[h];
-        hops.dlen[h] = hop_table[h].numel();
-      } else if (hop_table[h].dtype() == at::kInt) {
-        hops.table32[h] = reinterpret_cast<const uint32_t*>(
-            hop_table[h].data_ptr<int32_t>());
-      } else {
-        hops.table[h] = reinterpret_cast<const unsigned long long*>(
-            hop_table[h].data_ptr<int64_t>());
-      }
-      hops.tmask[h] = hop_table[h].numel() - 1;
-    }
-
-  }
+  ChainHops hops = chain_hops_from(hop_key32, hop_src, hop_table, hop_dmin);
   auto total = at::zeros({1}, seed_b.options().dtype(at::kLong));
   if (m > 0) {
     auto stream = cur_stream();
     int64_t n_tiles = (m + kChainTile - 1) / kChainTile;
     auto win = at::empty({n_tiles * hops.k * 2},
                          seed_b.options().dtype(at::kLong));
-    hipLaunchKernelGGL(chain_tile_bounds, dim3(grid_for(n_tiles)),
-                       dim3(kBlock), 0, stream,
-                       seed_b.data_ptr<int32_t>(), m, n_tiles, hops,
-                       win.data_ptr<int64_t>(),
-                       static_cast<unsigned long long*>(nullptr));
-    HIP_OK(hipGetLastError());
+    chain_bounds_launch(seed_b.data_ptr<int32_t>(), m, n_tiles, hops,
+                        win.data_ptr<int64_t>(), nullptr, stream);
     auto parts = at::zeros({kChainParts * kChainPartStride},
                            seed_b.options().dtype(at::kLong));
     chain_launch(seed_b.data_ptr<int32_t>(), seed_z.data_ptr<int32_t>(), m,
@@ -2255,102 +2135,129 @@ int64_t chain_count(at::Tensor seed_b, at::Tensor seed_z,
 
 // ------------------------------------------------------------ host launchers
 
-// shared emit phase for the K1 probes: per-probe-row emit for low fanout,
-// output-parallel balanced emit for skewed ranges.
-static std::vector<at::Tensor> emit_phase(at::Tensor key12, at::Tensor z,
-                                          at::Tensor lo, at::Tensor cnt,
-                                          int64_t m, hipStream_t stream) {
+// count phase of the K1 probes -> (lo, cnt) per probe row.  `sort_col`, when
+// given, is the one varying probe column: from kProbeSortedMin probes up, if
+// it ascends (and, with `need_nonneg`, starts non-negative: the low key half
+// compares unsigned) the merge-path count runs instead of the plain one.
+template <class Key>
+static std::pair<at::Tensor, at::Tensor> count_phase(
+    const at::Tensor& key12, Key key, int64_t m, const at::Tensor* sort_col,
+    bool need_nonneg, hipStream_t stream) {
+  auto n = key12.numel();
+  auto lo = at::empty({m}, key12.options());
+  auto cnt = at::empty({m}, key12.options().dtype(at::kInt));
+  if (m == 0) return {lo, cnt};
+  bool sorted = false;
+  if (sort_col && m >= kProbeSortedMin) {
+    // one cheap reduction decides the merge-path variant
+    const auto& col = *sort_col;
+    auto mono = at::all(col.slice(0, 1, m) >= col.slice(0, 0, m - 1));
+    sorted = (need_nonneg ? mono & (col[0] >= 0) : mono).item<bool>();
+  }
+  if (sorted) {
+    int64_t n_tiles = (m + kTile - 1) / kTile;
+    auto wlo = at::empty({n_tiles}, key12.options());
+    auto whi = at::empty({n_tiles}, key12.options());
+    hipLaunchKernelGGL(probe_tile_bounds<Key>, dim3(grid_for(n_tiles)),
+                       dim3(kBlock), 0, stream, key12.data_ptr<int64_t>(), n,
+                       key, m, n_tiles, wlo.data_ptr<int64_t>(),
+                       whi.data_ptr<int64_t>());
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL((probe_count<Key, true>), dim3(grid_for(m)),
+                       dim3(kBlock), 0, stream, key12.data_ptr<int64_t>(), n,
+                       key, m, wlo.data_ptr<int64_t>(),
+                       whi.data_ptr<int64_t>(), lo.data_ptr<int64_t>(),
+                       cnt.data_ptr<int32_t>());
+  } else {
+    hipLaunchKernelGGL((probe_count<Key, false>), dim3(grid_for(m)),
+                       dim3(kBlock), 0, stream, key12.data_ptr<int64_t>(), n,
+                       key, m, static_cast<const int64_t*>(nullptr),
+                       static_cast<const int64_t*>(nullptr),
+                       lo.data_ptr<int64_t>(), cnt.data_ptr<int32_t>());
+  }
+  HIP_OK(hipGetLastError());
+  return {lo, cnt};
+}
+
+// emit phase of the K1 probes -> (li, b, z, carried...): per-probe-row emit
+// for low fanout, output-parallel balanced emit for skewed ranges.  `carry`
+// brings k and the input columns; the outputs are allocated here.  Without
+// emit_b the b output stays empty.
+static std::vector<at::Tensor> emit_phase(const at::Tensor& key12,
+                                          const at::Tensor& z,
+                                          const at::Tensor& lo,
+                                          const at::Tensor& cnt, int64_t m,
+                                          CarryCols carry, bool emit_b,
+                                          hipStream_t stream) {
   auto opts_long = key12.options();
+  auto opts_int = z.options();
   auto offs = at::cumsum(cnt, 0, at::kLong);
   int64_t total = m > 0 ? offs[-1].item<int64_t>() : 0;
-  auto li = at::empty({total}, opts_long);
-  auto b = at::empty({total}, z.options());
-  auto zz = at::empty({total}, z.options());
-  if (total == 0) return {li, b, zz};
+  std::vector<at::Tensor> out = {at::empty({total}, opts_long),
+                                 at::empty({emit_b ? total : 0}, opts_int),
+                                 at::empty({total}, opts_int)};
+  for (int j = 0; j < carry.k; ++j) {
+    out.push_back(at::empty({total}, opts_int));
+    carry.out[j] = out.back().data_ptr<int32_t>();
+  }
+  if (total == 0) return out;
+  int64_t* li = out[0].data_ptr<int64_t>();
+  int32_t* b = emit_b ? out[1].data_ptr<int32_t>() : nullptr;
+  int32_t* zz = out[2].data_ptr<int32_t>();
   if (total >= 8 * m) {
     auto offs_full = at::zeros({m + 1}, opts_long);
     offs_full.narrow(0, 1, m).copy_(offs);
     hipLaunchKernelGGL(probe_emit_balanced, dim3(grid_for(total)),
                        dim3(kBlock), 0, stream, key12.data_ptr<int64_t>(),
                        z.data_ptr<int32_t>(), m, lo.data_ptr<int64_t>(),
-                       offs_full.data_ptr<int64_t>(), total,
-                       li.data_ptr<int64_t>(), b.data_ptr<int32_t>(),
-                       zz.data_ptr<int32_t>());
+                       offs_full.data_ptr<int64_t>(), total, carry, li, b, zz,
+                       emit_b);
   } else {
     auto offs_excl = offs - cnt.to(at::kLong);
     hipLaunchKernelGGL(probe_emit, dim3(grid_for(m)), dim3(kBlock), 0, stream,
                        key12.data_ptr<int64_t>(), z.data_ptr<int32_t>(), m,
                        lo.data_ptr<int64_t>(), cnt.data_ptr<int32_t>(),
-                       offs_excl.data_ptr<int64_t>(), li.data_ptr<int64_t>(),
-                       b.data_ptr<int32_t>(), zz.data_ptr<int32_t>());
+                       offs_excl.data_ptr<int64_t>(), carry, li, b, zz,
+                       emit_b);
   }
   HIP_OK(hipGetLastError());
-  return {li, b, zz};
+  return out;
+}
+
+static void check_exact_args(const at::Tensor& key12, const at::Tensor& keys) {
+  TORCH_CHECK(key12.is_cuda() && keys.is_cuda(),
+              "probe_exact: device tensors required");
+  TORCH_CHECK(key12.dtype() == at::kLong && keys.dtype() == at::kLong);
+}
+
+static void check_range_args(const at::Tensor& key12, const at::Tensor& vals) {
+  TORCH_CHECK(key12.is_cuda() && vals.is_cuda(),
+              "probe_range: device tensors required");
+  TORCH_CHECK(vals.dtype() == at::kInt);
 }
 
 // K1 probe — exact (packed 2-col key) mode.
 std::vector<at::Tensor> probe_exact(at::Tensor key12, at::Tensor z,
                                     at::Tensor keys) {
-  TORCH_CHECK(key12.is_cuda() && z.is_cuda() && keys.is_cuda(),
-              "probe_exact: device tensors required");
-  TORCH_CHECK(key12.dtype() == at::kLong && keys.dtype() == at::kLong);
-  TORCH_CHECK(z.dtype() == at::kInt);
+  check_exact_args(key12, keys);
+  TORCH_CHECK(z.is_cuda() && z.dtype() == at::kInt);
   auto m = keys.numel();
-  auto n = key12.numel();
-  auto lo = at::empty({m}, keys.options());
-  auto cnt = at::empty({m}, keys.options().dtype(at::kInt));
   auto stream = cur_stream();
-  if (m > 0) {
-    bool sorted = false;
-    if (m >= 262144) {
-      // one cheap reduction decides the merge-path variant
-      sorted = at::all(keys.slice(0, 1, m) >= keys.slice(0, 0, m - 1))
-                   .item<bool>();
-    }
-    if (sorted) {
-      int64_t n_tiles = (m + kTile - 1) / kTile;
-      auto wlo = at::empty({n_tiles}, keys.options());
-      auto whi = at::empty({n_tiles}, keys.options());
-      hipLaunchKernelGGL(tile_bounds, dim3(grid_for(n_tiles)), dim3(kBlock), 0,
-                         stream, key12.data_ptr<int64_t>(), n,
-                         keys.data_ptr<int64_t>(), m, n_tiles,
-                         wlo.data_ptr<int64_t>(), whi.data_ptr<int64_t>());
-      HIP_OK(hipGetLastError());
-      hipLaunchKernelGGL(probe_count_exact_sorted, dim3(grid_for(m)),
-                         dim3(kBlock), 0, stream, key12.data_ptr<int64_t>(),
-                         keys.data_ptr<int64_t>(), m, wlo.data_ptr<int64_t>(),
-                         whi.data_ptr<int64_t>(), lo.data_ptr<int64_t>(),
-                         cnt.data_ptr<int32_t>());
-      HIP_OK(hipGetLastError());
-    } else {
-      hipLaunchKernelGGL(probe_count_exact, dim3(grid_for(m)), dim3(kBlock), 0,
-                         stream, key12.data_ptr<int64_t>(), n,
-                         keys.data_ptr<int64_t>(), m, lo.data_ptr<int64_t>(),
-                         cnt.data_ptr<int32_t>());
-      HIP_OK(hipGetLastError());
-    }
-  }
-  return emit_phase(key12, z, lo, cnt, m, stream);
+  auto [lo, cnt] = count_phase(key12, ExactKey{keys.data_ptr<int64_t>()}, m,
+                               &keys, false, stream);
+  return emit_phase(key12, z, lo, cnt, m, CarryCols{}, true, stream);
 }
 
 // K1 probe — range (1-col prefix) mode.
 std::vector<at::Tensor> probe_range(at::Tensor key12, at::Tensor z,
                                     at::Tensor vals) {
-  TORCH_CHECK(key12.is_cuda() && z.is_cuda() && vals.is_cuda());
-  TORCH_CHECK(vals.dtype() == at::kInt);
+  check_range_args(key12, vals);
+  TORCH_CHECK(z.is_cuda());
   auto m = vals.numel();
-  auto n = key12.numel();
-  auto lo = at::empty({m}, key12.options());
-  auto cnt = at::empty({m}, vals.options());
   auto stream = cur_stream();
-  if (m > 0) {
-    hipLaunchKernelGGL(probe_count_range, dim3(grid_for(m)), dim3(kBlock), 0,
-                       stream, key12.data_ptr<int64_t>(), n,
-                       vals.data_ptr<int32_t>(), m, lo.data_ptr<int64_t>(),
-                       cnt.data_ptr<int32_t>());
-    HIP_OK(hipGetLastError());
-  }
-  return emit_phase(key12, z, lo, cnt, m, stream);
+  auto [lo, cnt] = count_phase(key12, RangeKey{vals.data_ptr<int32_t>()}, m,
+                               nullptr, false, stream);
+  return emit_phase(key12, z, lo, cnt, m, CarryCols{}, true, stream);
 }
 
 // K1 fused probe: inline key packing, optional merge-path for sorted keys,
@@ -2367,16 +2274,23 @@ std::vector<at::Tensor> probe_fused(at::Tensor key12, at::Tensor z,
   int64_t m = a_col.has_value() ? a_col->numel()
                                 : (b_col.has_value() ? b_col->numel() : 0);
   TORCH_CHECK(m > 0, "probe_fused: need at least one probe column");
-  auto n = key12.numel();
-  auto opts_long = key12.options();
-  auto opts_int = z.options();
-  const int32_t* a_ptr = a_col.has_value() ? a_col->data_ptr<int32_t>() : nullptr;
-  const int32_t* b_ptr = b_col.has_value() ? b_col->data_ptr<int32_t>() : nullptr;
+  CarryCols carry{};
+  carry.k = static_cast<int>(carry_cols.size());
+  for (size_t j = 0; j < carry_cols.size(); ++j) {
+    TORCH_CHECK(carry_cols[j].is_cuda()
+                && carry_cols[j].dtype() == at::kInt
+                && carry_cols[j].numel() == m);
+    carry.in[j] = carry_cols[j].data_ptr<int32_t>();
+  }
+  FusedKey key{a_col.has_value() ? a_col->data_ptr<int32_t>() : nullptr,
+               a_const,
+               b_col.has_value() ? b_col->data_ptr<int32_t>() : nullptr,
+               b_const};
   // constant leading component: narrow every search to that contiguous
   // region ONCE (e.g. one predicate's slice) — the region usually stays
   // cache-resident, cutting the dependent-load chain per probe
-  if (!a_ptr && n > 0) {
-    auto reg_keys = at::empty({2}, opts_long);
+  if (!key.a_col && key12.numel() > 0) {
+    auto reg_keys = at::empty({2}, key12.options());
     reg_keys[0] = (a_const << 32);
     reg_keys[1] = (a_const << 32) | 0xFFFFFFFFLL;
     auto lo_t = at::searchsorted(key12, reg_keys[0], false, false);
@@ -2385,228 +2299,127 @@ std::vector<at::Tensor> probe_fused(at::Tensor key12, at::Tensor z,
     int64_t rend = hi_t.item<int64_t>();
     key12 = key12.narrow(0, roff, rend - roff);
     z = z.narrow(0, roff, rend - roff);
-    n = rend - roff;
   }
-  auto lo = at::empty({m}, opts_long);
-  auto cnt = at::empty({m}, opts_int);
-  auto stream = cur_stream();
   // merge-path when the single varying column is sorted (signed order is
   // the packed order when values share a sign; negatives skip the check)
-  bool sorted = false;
-  if (m >= 262144 && (a_ptr == nullptr) != (b_ptr == nullptr)) {
-    const auto& col = a_col.has_value() ? *a_col : *b_col;
-    bool need_nonneg = b_col.has_value();  // low 32 bits compare unsigned
-    auto mono = at::all(col.slice(0, 1, m) >= col.slice(0, 0, m - 1));
-    if (need_nonneg) {
-      sorted = (mono & (col[0] >= 0)).item<bool>();
-    } else {
-      sorted = mono.item<bool>();
-    }
-  }
-  if (sorted) {
-    int64_t n_tiles = (m + kTile - 1) / kTile;
-    auto wlo = at::empty({n_tiles}, opts_long);
-    auto whi = at::empty({n_tiles}, opts_long);
-    hipLaunchKernelGGL(tile_bounds_fused, dim3(grid_for(n_tiles)),
-                       dim3(kBlock), 0, stream, key12.data_ptr<int64_t>(), n,
-                       a_ptr, a_const, b_ptr, b_const, m, n_tiles,
-                       wlo.data_ptr<int64_t>(), whi.data_ptr<int64_t>());
-    HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(probe_count_fused_sorted, dim3(grid_for(m)),
-                       dim3(kBlock), 0, stream, key12.data_ptr<int64_t>(),
-                       a_ptr, a_const, b_ptr, b_const, m,
-                       wlo.data_ptr<int64_t>(), whi.data_ptr<int64_t>(),
-                       lo.data_ptr<int64_t>(), cnt.data_ptr<int32_t>());
-  } else {
-    hipLaunchKernelGGL(probe_count_fused, dim3(grid_for(m)), dim3(kBlock), 0,
-                       stream, key12.data_ptr<int64_t>(), n, a_ptr, a_const,
-                       b_ptr, b_const, m, lo.data_ptr<int64_t>(),
-                       cnt.data_ptr<int32_t>());
-  }
-  HIP_OK(hipGetLastError());
-  auto offs = at::cumsum(cnt, 0, at::kLong);
-  int64_t total = offs[-1].item<int64_t>();
-  auto li = at::empty({total}, opts_long);
-  auto b_out = at::empty({emit_b ? total : 0}, opts_int);
-  auto zz = at::empty({total}, opts_int);
-  CarryCols carry{};
-  carry.k = static_cast<int>(carry_cols.size());
-  std::vector<at::Tensor> carried;
-  for (size_t j = 0; j < carry_cols.size(); ++j) {
-    TORCH_CHECK(carry_cols[j].is_cuda()
-                && carry_cols[j].dtype() == at::kInt
-                && carry_cols[j].numel() == m);
-    carry.in[j] = carry_cols[j].data_ptr<int32_t>();
-    carried.push_back(at::empty({total}, opts_int));
-    carry.out[j] = carried.back().data_ptr<int32_t>();
-  }
-  if (total > 0) {
-    int32_t* b_ptr_out = emit_b ? b_out.data_ptr<int32_t>() : nullptr;
-    if (total >= 8 * m) {
-      auto offs_full = at::zeros({m + 1}, opts_long);
-      offs_full.narrow(0, 1, m).copy_(offs);
-      hipLaunchKernelGGL(probe_emit_carry_balanced, dim3(grid_for(total)),
-                         dim3(kBlock), 0, stream, key12.data_ptr<int64_t>(),
-                         z.data_ptr<int32_t>(), m, lo.data_ptr<int64_t>(),
-                         offs_full.data_ptr<int64_t>(), total, carry,
-                         li.data_ptr<int64_t>(), b_ptr_out,
-                         zz.data_ptr<int32_t>(), emit_b);
-    } else {
-      auto offs_excl = offs - cnt.to(at::kLong);
-      hipLaunchKernelGGL(probe_emit_carry, dim3(grid_for(m)), dim3(kBlock), 0,
-                         stream, key12.data_ptr<int64_t>(),
-                         z.data_ptr<int32_t>(), m, lo.data_ptr<int64_t>(),
-                         cnt.data_ptr<int32_t>(), offs_excl.data_ptr<int64_t>(),
-                         carry, li.data_ptr<int64_t>(), b_ptr_out,
-                         zz.data_ptr<int32_t>(), emit_b);
-    }
-    HIP_OK(hipGetLastError());
-  }
-  std::vector<at::Tensor> out = {li, b_out, zz};
-  for (auto& t : carried) out.push_back(t);
-  return out;
+  const at::Tensor* sort_col = nullptr;
+  if ((key.a_col == nullptr) != (key.b_col == nullptr))
+    sort_col = a_col.has_value() ? &*a_col : &*b_col;
+  auto stream = cur_stream();
+  auto [lo, cnt] = count_phase(key12, key, m, sort_col, b_col.has_value(),
+                               stream);
+  return emit_phase(key12, z, lo, cnt, m, carry, emit_b, stream);
 }
 
 // K1 count-only variants: COUNT(*) queries skip the emit pass entirely.
 at::Tensor probe_exact_counts(at::Tensor key12, at::Tensor keys) {
-  TORCH_CHECK(key12.is_cuda() && keys.is_cuda());
-  auto m = keys.numel();
-  auto n = key12.numel();
-  auto lo = at::empty({m}, keys.options());
-  auto cnt = at::empty({m}, keys.options().dtype(at::kInt));
-  if (m > 0) {
-    hipLaunchKernelGGL(probe_count_exact, dim3(grid_for(m)), dim3(kBlock), 0,
-                       cur_stream(), key12.data_ptr<int64_t>(), n,
-                       keys.data_ptr<int64_t>(), m, lo.data_ptr<int64_t>(),
-                       cnt.data_ptr<int32_t>());
-    HIP_OK(hipGetLastError());
-  }
-  return cnt;
+  check_exact_args(key12, keys);
+  return count_phase(key12, ExactKey{keys.data_ptr<int64_t>()}, keys.numel(),
+                     nullptr, false, cur_stream()).second;
 }
 
 at::Tensor probe_range_counts(at::Tensor key12, at::Tensor vals) {
-  TORCH_CHECK(key12.is_cuda() && vals.is_cuda());
-  auto m = vals.numel();
-  auto n = key12.numel();
-  auto lo = at::empty({m}, key12.options());
-  auto cnt = at::empty({m}, vals.options());
-  if (m > 0) {
-    hipLaunchKernelGGL(probe_count_range, dim3(grid_for(m)), dim3(kBlock), 0,
-                       cur_stream(), key12.data_ptr<int64_t>(), n,
-                       vals.data_ptr<int32_t>(), m, lo.data_ptr<int64_t>(),
-                       cnt.data_ptr<int32_t>());
-    HIP_OK(hipGetLastError());
+  check_range_args(key12, vals);
+  return count_phase(key12, RangeKey{vals.data_ptr<int32_t>()}, vals.numel(),
+                     nullptr, false, cur_stream()).second;
+}
+
+// The two sides of a K2 join, validated: int32 device columns, the same
+// number (1..kMaxKeyCols) on each side.
+struct HjSides {
+  KeyCols probe, build;
+  int64_t l, r;
+};
+
+static HjSides hj_sides(const std::vector<at::Tensor>& left_cols,
+                        const std::vector<at::Tensor>& right_cols) {
+  TORCH_CHECK(!left_cols.empty() && left_cols.size() == right_cols.size());
+  TORCH_CHECK(left_cols.size() <= kMaxKeyCols, "hash_join: at most 4 key cols");
+  HjSides s{};
+  s.probe.k = s.build.k = static_cast<int>(left_cols.size());
+  for (size_t j = 0; j < left_cols.size(); ++j) {
+    TORCH_CHECK(left_cols[j].is_cuda() && right_cols[j].is_cuda());
+    TORCH_CHECK(left_cols[j].dtype() == at::kInt && right_cols[j].dtype() == at::kInt);
+    s.probe.c[j] = left_cols[j].data_ptr<int32_t>();
+    s.build.c[j] = right_cols[j].data_ptr<int32_t>();
   }
+  s.l = left_cols[0].numel();
+  s.r = right_cols[0].numel();
+  return s;
+}
+
+// The chained table over the build side.  Up to kHjLdsRows build rows each
+// block stages its own in LDS, and this one stays empty.
+struct HjTable {
+  bool lds;
+  at::Tensor heads, next;
+  uint32_t mask = 0;
+};
+
+static HjTable hj_table(const HjSides& s, const at::TensorOptions& opts_int,
+                        hipStream_t stream) {
+  HjTable t{s.r <= kHjLdsRows, at::empty({0}, opts_int),
+            at::empty({0}, opts_int)};
+  if (t.lds) return t;
+  // table size: next pow2 >= 2r
+  uint64_t h = 1;
+  while (h < static_cast<uint64_t>(2 * s.r)) h <<= 1;
+  t.mask = static_cast<uint32_t>(h - 1);
+  t.heads = at::full({static_cast<int64_t>(h)}, -1, opts_int);
+  t.next = at::empty({s.r}, opts_int);
+  hipLaunchKernelGGL(hj_build, dim3(grid_for(s.r)), dim3(kBlock), 0, stream,
+                     s.build, s.r, t.mask, t.heads.data_ptr<int32_t>(),
+                     t.next.data_ptr<int32_t>());
+  HIP_OK(hipGetLastError());
+  return t;
+}
+
+// per-probe-row match counts; both sides non-empty
+static at::Tensor hj_counts(const HjSides& s, const HjTable& t,
+                            const at::TensorOptions& opts_int,
+                            hipStream_t stream) {
+  auto cnt = at::empty({s.l}, opts_int);
+  hipLaunchKernelGGL(t.lds ? hj_count<true> : hj_count<false>,
+                     dim3(grid_for(s.l)), dim3(kBlock), 0, stream, s.probe,
+                     s.l, s.build, s.r, t.heads.data_ptr<int32_t>(),
+                     t.next.data_ptr<int32_t>(), t.mask,
+                     cnt.data_ptr<int32_t>());
+  HIP_OK(hipGetLastError());
   return cnt;
 }
 
 // K2 hash join, count-only: per-probe-row match counts (no emit).
 at::Tensor hash_join_counts(std::vector<at::Tensor> left_cols,
                             std::vector<at::Tensor> right_cols) {
-  TORCH_CHECK(!left_cols.empty() && left_cols.size() == right_cols.size());
-  TORCH_CHECK(left_cols.size() <= kMaxKeyCols);
-  int64_t l = left_cols[0].numel();
-  int64_t r = right_cols[0].numel();
-  auto opts_int = left_cols[0].options().dtype(at::kInt);
-  if (l == 0 || r == 0) return at::zeros({l}, opts_int);
-  KeyCols probe{}, build{};
-  probe.k = build.k = static_cast<int>(left_cols.size());
-  for (size_t j = 0; j < left_cols.size(); ++j) {
-    probe.c[j] = left_cols[j].data_ptr<int32_t>();
-    build.c[j] = right_cols[j].data_ptr<int32_t>();
-  }
+  HjSides s = hj_sides(left_cols, right_cols);
+  auto opts_int = left_cols[0].options();
+  if (s.l == 0 || s.r == 0) return at::zeros({s.l}, opts_int);
   auto stream = cur_stream();
-  auto cnt = at::empty({l}, opts_int);
-  if (r <= kHjLdsRows) {
-    hipLaunchKernelGGL(hj_count_lds, dim3(grid_for(l)), dim3(kBlock), 0,
-                       stream, probe, l, build, r, cnt.data_ptr<int32_t>());
-    HIP_OK(hipGetLastError());
-    return cnt;
-  }
-  uint64_t h = 1;
-  while (h < static_cast<uint64_t>(2 * r)) h <<= 1;
-  uint32_t mask = static_cast<uint32_t>(h - 1);
-  auto heads = at::full({static_cast<int64_t>(h)}, -1, opts_int);
-  auto next = at::empty({r}, opts_int);
-  hipLaunchKernelGGL(hj_build, dim3(grid_for(r)), dim3(kBlock), 0, stream,
-                     build, r, mask, heads.data_ptr<int32_t>(),
-                     next.data_ptr<int32_t>());
-  HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(hj_count, dim3(grid_for(l)), dim3(kBlock), 0, stream,
-                     probe, l, build, heads.data_ptr<int32_t>(),
-                     next.data_ptr<int32_t>(), mask, cnt.data_ptr<int32_t>());
-  HIP_OK(hipGetLastError());
-  return cnt;
+  return hj_counts(s, hj_table(s, opts_int, stream), opts_int, stream);
 }
 
 // K2 hash join: returns (li, ri) index pairs; multiset semantics.
 std::vector<at::Tensor> hash_join(std::vector<at::Tensor> left_cols,
                                   std::vector<at::Tensor> right_cols) {
-  TORCH_CHECK(!left_cols.empty() && left_cols.size() == right_cols.size());
-  TORCH_CHECK(left_cols.size() <= kMaxKeyCols, "hash_join: at most 4 key cols");
-  int64_t l = left_cols[0].numel();
-  int64_t r = right_cols[0].numel();
-  auto opts_long = left_cols[0].options().dtype(at::kLong);
-  auto opts_int = left_cols[0].options().dtype(at::kInt);
-  if (l == 0 || r == 0) {
+  HjSides s = hj_sides(left_cols, right_cols);
+  auto opts_int = left_cols[0].options();
+  auto opts_long = opts_int.dtype(at::kLong);
+  if (s.l == 0 || s.r == 0) {
     return {at::empty({0}, opts_long), at::empty({0}, opts_long)};
   }
-  KeyCols probe{}, build{};
-  probe.k = build.k = static_cast<int>(left_cols.size());
-  for (size_t j = 0; j < left_cols.size(); ++j) {
-    TORCH_CHECK(left_cols[j].is_cuda() && right_cols[j].is_cuda());
-    TORCH_CHECK(left_cols[j].dtype() == at::kInt && right_cols[j].dtype() == at::kInt);
-    probe.c[j] = left_cols[j].data_ptr<int32_t>();
-    build.c[j] = right_cols[j].data_ptr<int32_t>();
-  }
   auto stream = cur_stream();
-  bool lds = r <= kHjLdsRows;
-  at::Tensor heads, next;
-  uint32_t mask = 0;
-  if (lds) {
-    // small build side: each block stages the chained table in LDS
-    auto cnt = at::empty({l}, opts_int);
-    hipLaunchKernelGGL(hj_count_lds, dim3(grid_for(l)), dim3(kBlock), 0,
-                       stream, probe, l, build, r, cnt.data_ptr<int32_t>());
-    HIP_OK(hipGetLastError());
-    auto offs = at::cumsum(cnt, 0, at::kLong);
-    int64_t total = offs[-1].item<int64_t>();
-    auto offs_excl = offs - cnt.to(at::kLong);
-    auto li = at::empty({total}, opts_long);
-    auto ri = at::empty({total}, opts_long);
-    if (total > 0) {
-      hipLaunchKernelGGL(hj_emit_lds, dim3(grid_for(l)), dim3(kBlock), 0,
-                         stream, probe, l, build, r,
-                         offs_excl.data_ptr<int64_t>(),
-                         li.data_ptr<int64_t>(), ri.data_ptr<int64_t>());
-      HIP_OK(hipGetLastError());
-    }
-    return {li, ri};
-  }
-  // table size: next pow2 >= 2r
-  uint64_t h = 1;
-  while (h < static_cast<uint64_t>(2 * r)) h <<= 1;
-  mask = static_cast<uint32_t>(h - 1);
-  heads = at::full({static_cast<int64_t>(h)}, -1, opts_int);
-  next = at::empty({r}, opts_int);
-  hipLaunchKernelGGL(hj_build, dim3(grid_for(r)), dim3(kBlock), 0, stream,
-                     build, r, mask, heads.data_ptr<int32_t>(),
-                     next.data_ptr<int32_t>());
-  HIP_OK(hipGetLastError());
-  auto cnt = at::empty({l}, opts_int);
-  hipLaunchKernelGGL(hj_count, dim3(grid_for(l)), dim3(kBlock), 0, stream,
-                     probe, l, build, heads.data_ptr<int32_t>(),
-                     next.data_ptr<int32_t>(), mask, cnt.data_ptr<int32_t>());
-  HIP_OK(hipGetLastError());
+  HjTable t = hj_table(s, opts_int, stream);
+  auto cnt = hj_counts(s, t, opts_int, stream);
   auto offs = at::cumsum(cnt, 0, at::kLong);
   int64_t total = offs[-1].item<int64_t>();
   auto offs_excl = offs - cnt.to(at::kLong);
   auto li = at::empty({total}, opts_long);
   auto ri = at::empty({total}, opts_long);
   if (total > 0) {
-    hipLaunchKernelGGL(hj_emit, dim3(grid_for(l)), dim3(kBlock), 0, stream,
-                       probe, l, build, heads.data_ptr<int32_t>(),
-                       next.data_ptr<int32_t>(), mask,
+    hipLaunchKernelGGL(t.lds ? hj_emit<true> : hj_emit<false>,
+                       dim3(grid_for(s.l)), dim3(kBlock), 0, stream, s.probe,
+                       s.l, s.build, s.r, t.heads.data_ptr<int32_t>(),
+                       t.next.data_ptr<int32_t>(), t.mask,
                        offs_excl.data_ptr<int64_t>(), li.data_ptr<int64_t>(),
                        ri.data_ptr<int64_t>());
     HIP_OK(hipGetLastError());
@@ -4673,6 +4486,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K2 chained hash join over int32 key columns -> (li, ri)");
   m.def("chain_tile", []() { return static_cast<int64_t>(kChainTile); },
         "seed rows per chain tile (win buffer sizing)");
+  m.def("probe_sorted_min", []() { return kProbeSortedMin; },
+        "fewest probe rows at which a sorted probe column takes the "
+        "merge-path count");
   m.def("chain_span", []() { return static_cast<int64_t>(kChainSpan); },
         "widest key span a tile's window is counted by direct address, and "
         "the most window rows a tile stages for the LDS merge");
