@@ -1840,10 +1840,14 @@ chain_count_kernel(const int32_t* __restrict__ seed_b,
     atomicAdd(parts + (blockIdx.x % n_parts) * kChainPartStride, acc);
 }
 
-// total = sum of the partial sums, which are left zeroed for the next query
+// total = sum of the partial sums, which are left zeroed for the next query.
+// With `host_out` (the device address of 16 host-mapped pinned bytes) the
+// count goes straight to the host instead: count, a system-scope fence, then
+// the flag the host spins on, so that no copy command follows the kernel.
 __global__ void __launch_bounds__(kChainParts)
 chain_total_kernel(unsigned long long* __restrict__ parts,
-                   unsigned long long* __restrict__ total) {
+                   unsigned long long* __restrict__ total,
+                   unsigned long long* __restrict__ host_out) {
   __shared__ unsigned long long wave_sum[kChainParts / 64];
   unsigned long long v = parts[threadIdx.x * kChainPartStride];
   parts[threadIdx.x * kChainPartStride] = 0;
@@ -1854,8 +1858,324 @@ chain_total_kernel(unsigned long long* __restrict__ parts,
     unsigned long long sum = 0;
 #pragma unroll
     for (int i = 0; i < kChainParts / 64; ++i) sum += wave_sum[i];
-    *total = sum;
+    if (host_out) {
+      // one release fence between the two stores: the count has left the
+      // device before the flag does
+      __hip_atomic_store(host_out, sum, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+      __hip_atomic_store(host_out + 1, 1ull, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+    } else {
+      *total = sum;
+    }
   }
+}
+
+// ---- packed tiles for the direct-count shape ------------------------------
+// A registration whose every tile is counted directly (last - first <
+// kChainSpan) needs 11 bits of a seed's key and of a window row's key once
+// the tile's first key is known, so the serve path re-encodes its three
+// streamed columns once, frame-of-reference per tile, 6 B per seed where
+// the columns take 12:
+//   seeds  one u32 per seed, (b - first_t) | ((z - zmin) << kPackKeyBits),
+//          padded with zeros to whole tiles;
+//   rows   one u16 per window row, key - first_t, each tile's rows padded to
+//          a multiple of kPackChunk (16 bytes) with kPackPadRow, whose bin
+//          lies behind the last one a seed can read;
+//          (both permuted within the tile, see chain_pack_seed_at)
+//   recs   per tile {first_t, the rows' offset and count in chunks,
+//          last_t - first_t + 1}.
+// The rule (chain_pack_rule_kernel and register_chain_serve):
+//   the chain is exactly one src-0 search hop hp plus at most one direct or
+//   table32 hop ht; every tile has last - first < kChainSpan and a window of
+//   0 rows or more than lds_min; if ht reads z, max(z) - min(z) < 2^21; the
+//   windows together hold at most 2 * (m + n_hp) rows (a key run that
+//   straddles tiles repeats in each); a direct table ends below 2^32 and
+//   neither table has more than 2^30 slots (byte offsets stay in 32 bits);
+//   KOLIBRIE_CHAIN_PACKED is not 0.  Anything else keeps the columns.
+constexpr int kPackKeyBits = 11;
+constexpr int kPackZBits = 32 - kPackKeyBits;
+constexpr int kPackChunk = 8;
+constexpr uint32_t kPackPadRow = kChainSpan;
+static_assert((1 << kPackKeyBits) == kChainSpan, "a key offset is 11 bits");
+static_assert(kChainPad >= 1, "the pad rows' bin lies behind the slice");
+// rows that travel with the tile's loads: two dwordx4 per lane
+constexpr int kPackPreChunks = 2 * kChainWave;
+
+enum ChainPackStat { kPackBad = 0, kPackRows = 1, kPackZMaxInv = 2,
+                     kPackZMax = 3, kPackStats = 4 };
+
+// the per-tile half of the rule, the tiles' row chunks (for the offsets)
+// and the row total
+__global__ void chain_pack_rule_kernel(
+    const int32_t* __restrict__ seed_b, int64_t m, int64_t n_tiles,
+    const int64_t* __restrict__ win, int k, int hp, int lds_min,
+    int64_t* __restrict__ chunks, unsigned long long* __restrict__ stats) {
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n_tiles;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t first = static_cast<uint32_t>(seed_b[t * kChainTile]);
+    uint32_t last =
+        static_cast<uint32_t>(seed_b[min((t + 1) * kChainTile, m) - 1]);
+    int64_t span = win[(t * k + hp) * 2 + 1] - win[(t * k + hp) * 2];
+    bool ok = last - first < static_cast<uint32_t>(kChainSpan)
+        && (span == 0 || span > lds_min);
+    chunks[t] = (span + kPackChunk - 1) / kPackChunk;
+    if (!ok) atomicOr(stats + kPackBad, 1ull);
+    if (span)
+      atomicAdd(stats + kPackRows, static_cast<unsigned long long>(span));
+  }
+}
+
+// min and max of z as unsigned values (the min as the max of ~z, so that
+// zeroed stats are the identity of both)
+__global__ void chain_pack_zrange_kernel(
+    const int32_t* __restrict__ seed_z, int64_t m,
+    unsigned long long* __restrict__ stats) {
+  uint32_t hi = 0, inv = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < m;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t z = static_cast<uint32_t>(seed_z[i]);
+    hi = max(hi, z);
+    inv = max(inv, ~z);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    hi = max(hi, static_cast<uint32_t>(__shfl_down(hi, off)));
+    inv = max(inv, static_cast<uint32_t>(__shfl_down(inv, off)));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(stats + kPackZMax, static_cast<unsigned long long>(hi));
+    atomicMax(stats + kPackZMaxInv, static_cast<unsigned long long>(inv));
+  }
+}
+
+// Place i of a packed tile holds the tile's seed chain_pack_seed_at(i): a
+// lane's dwordx4 takes every 64th seed of its group of 256, and likewise a
+// lane's chunk takes every c-th row of the c <= 64 chunks loaded together.
+// Sums do not mind the order, and the 64 lanes of one bin read or row add
+// then go to neighbouring keys' bins, which lie in different LDS banks
+// (consecutive seeds or rows in a lane put them 4 and 8 bins apart).
+__host__ __device__ __forceinline__ int chain_pack_seed_at(int i) {
+  return (i & ~255) | ((i & 3) << 6) | ((i >> 2) & 63);
+}
+
+// one block per tile (grid-stride): the tile's seeds, rows and record.
+// `offs` is the inclusive prefix sum of the tiles' chunk counts.
+__global__ void __launch_bounds__(kBlock)
+chain_pack_tiles_kernel(const int32_t* __restrict__ seed_b,
+                        const int32_t* __restrict__ seed_z, int64_t m,
+                        int64_t n_tiles, const int32_t* __restrict__ key32,
+                        const int64_t* __restrict__ win, int k, int hp,
+                        const int64_t* __restrict__ offs, uint32_t zmin,
+                        bool use_z, uint32_t* __restrict__ pseeds,
+                        uint16_t* __restrict__ prows,
+                        uint4* __restrict__ recs) {
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    uint32_t first = static_cast<uint32_t>(seed_b[t * kChainTile]);
+    uint32_t last =
+        static_cast<uint32_t>(seed_b[min((t + 1) * kChainTile, m) - 1]);
+    int64_t lo = win[(t * k + hp) * 2];
+    int64_t span = win[(t * k + hp) * 2 + 1] - lo;
+    int64_t chunks = (span + kPackChunk - 1) / kPackChunk;
+    int64_t off = offs[t] - chunks;
+    for (int i = threadIdx.x; i < kChainTile; i += kBlock) {
+      int64_t idx = t * kChainTile + chain_pack_seed_at(i);
+      uint32_t v = 0;
+      if (idx < m) {
+        v = static_cast<uint32_t>(seed_b[idx]) - first;
+        if (use_z)
+          v |= (static_cast<uint32_t>(seed_z[idx]) - zmin) << kPackKeyBits;
+      }
+      pseeds[t * kChainTile + i] = v;
+    }
+    uint16_t* rows = prows + off * kPackChunk;
+    for (int64_t r = threadIdx.x; r < chunks * kPackChunk; r += kBlock) {
+      // the block of up to kChainWave chunks this one is loaded with, and
+      // the row it holds at this place
+      int64_t blk = r / (kPackChunk * kChainWave);
+      int64_t c = min<int64_t>(kChainWave, chunks - blk * kChainWave);
+      int64_t in_blk = r % (kPackChunk * kChainWave);
+      int64_t row = blk * (kPackChunk * kChainWave)
+          + (in_blk % kPackChunk) * c + in_blk / kPackChunk;
+      rows[r] = static_cast<uint16_t>(
+          row < span ? static_cast<uint32_t>(key32[lo + row]) - first
+                     : kPackPadRow);
+    }
+    if (threadIdx.x == 0)
+      recs[t] = make_uint4(first, static_cast<uint32_t>(off),
+                           static_cast<uint32_t>(chunks), last - first + 1);
+  }
+}
+
+// the packed kernel's one further hop, with everything in 32 bits: the
+// probed value is base + rel, where rel is the seed's key or z offset
+enum ChainPackHt { kPackHtNone = 0, kPackHtDirect = 1, kPackHtTable32 = 2 };
+struct ChainPackedHt {
+  const uint32_t* tab;
+  uint32_t kind, src;
+  uint32_t zmin;
+  uint32_t dmin, dlast;  // direct: slots [0, dlast] hold values dmin + slot
+  uint32_t mask;         // table32
+};
+
+__device__ __forceinline__ uint32_t chain_pack_tab(const uint32_t* tab,
+                                                   uint32_t slot) {
+  // slot < 2^30: the byte offset stays a 32-bit register beside the base
+  return *reinterpret_cast<const uint32_t*>(
+      reinterpret_cast<const char*>(tab) + (slot << 2));
+}
+
+// one 8-row chunk into the bins: no index is checked, pad rows land in the
+// bin behind the slice's last key
+__device__ __forceinline__ void chain_pack_add(uint32_t* lds, const uint4& c) {
+  uint32_t w[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    __hip_atomic_fetch_add(&lds[w[i] & 0xFFFFu], 1u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(&lds[w[i] >> 16], 1u, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+}
+
+// a seed's probe offset: its key bits (src 0) or its z bits (src 1), by a
+// wave-uniform shift and width, so that the hop's source costs no branch
+__device__ __forceinline__ uint32_t chain_pack_rel(uint32_t seed,
+                                                   uint32_t shift,
+                                                   uint32_t bits) {
+  return __builtin_amdgcn_ubfe(seed, shift, bits);
+}
+
+// bin reads and the probe's finish for one tile.  `valid` seeds of the tile
+// exist (the rest are padding, dropped by index in the tail tile).
+template <int kKind, bool kTail>
+__device__ __forceinline__ unsigned long long chain_packed_finish(
+    const uint32_t* lds, const uint4 (&p)[kChainGroups],
+    const uint32_t (&raw)[kChainGroups][kChainSeeds], const ChainPackedHt& ht,
+    uint32_t base, uint32_t shift, uint32_t bits, uint32_t valid) {
+  unsigned long long acc = 0;
+#pragma unroll
+  for (int g = 0; g < kChainGroups; ++g) {
+    uint32_t s[kChainSeeds] = {p[g].x, p[g].y, p[g].z, p[g].w};
+#pragma unroll
+    for (int u = 0; u < kChainSeeds; ++u) {
+      uint32_t cnt = lds[s[u] & (kChainSpan - 1)];
+      uint32_t mul = 1;
+      if (kKind == kPackHtDirect) {
+        uint32_t off = chain_pack_rel(s[u], shift, bits) + (base - ht.dmin);
+        mul = off <= ht.dlast ? raw[g][u] : 0u;
+      } else if (kKind == kPackHtTable32) {
+        uint32_t v = base + chain_pack_rel(s[u], shift, bits);
+        uint32_t slot = h32(v) & ht.mask;
+        uint32_t e = raw[g][u];
+        while (e != kTbl32Empty && (e >> 7) != v) {
+          slot = (slot + 1) & ht.mask;
+          e = chain_pack_tab(ht.tab, slot);
+        }
+        mul = e == kTbl32Empty ? 0u : (e & 0x7Fu);
+      }
+      if (kTail) {
+        uint32_t i = chain_pack_seed_at(
+            (g * kChainWave + threadIdx.x) * kChainSeeds + u);
+        mul = i < valid ? mul : 0u;
+      }
+      // the one product that can pass 32 bits
+      acc += static_cast<unsigned long long>(cnt) * mul;
+    }
+  }
+  return acc;
+}
+
+// a wave's tiles, for one kind of further hop
+template <int kKind>
+__device__ __forceinline__ unsigned long long chain_packed_tiles(
+    uint32_t* lds, const uint4* __restrict__ pseeds,
+    const uint4* __restrict__ prows, const uint4* __restrict__ recs,
+    int64_t m, int64_t n_tiles, const ChainPackedHt& ht) {
+  unsigned long long acc = 0;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t pad2 = kPackPadRow * 0x10001u;
+  const uint4 pad_chunk = make_uint4(pad2, pad2, pad2, pad2);
+  const uint32_t shift = ht.src == 0 ? 0 : kPackKeyBits;
+  const uint32_t bits = ht.src == 0 ? kPackKeyBits : kPackZBits;
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const uint4 rec = recs[t];
+    const uint32_t chunks = rec.z, nkeys = rec.w;
+    const uint32_t base = ht.src == 0 ? rec.x : ht.zmin;
+    // every load of the tile, back to back
+    uint4 p[kChainGroups];
+    const uint4* seeds = pseeds + t * (kChainTile / 4) + lane;
+#pragma unroll
+    for (int g = 0; g < kChainGroups; ++g) p[g] = seeds[g * kChainWave];
+    const uint4* rows = prows + rec.y;
+    uint4 rw[2] = {pad_chunk, pad_chunk};
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      if (lane + j * kChainWave < chunks) rw[j] = rows[lane + j * kChainWave];
+    // the further hop's first probe, not waited for
+    uint32_t raw[kChainGroups][kChainSeeds];
+    if (kKind != kPackHtNone) {
+#pragma unroll
+      for (int g = 0; g < kChainGroups; ++g) {
+        uint32_t s[kChainSeeds] = {p[g].x, p[g].y, p[g].z, p[g].w};
+#pragma unroll
+        for (int u = 0; u < kChainSeeds; ++u) {
+          uint32_t rel = chain_pack_rel(s[u], shift, bits);
+          if (kKind == kPackHtDirect) {
+            uint32_t off = rel + (base - ht.dmin);
+            raw[g][u] = chain_pack_tab(ht.tab, off <= ht.dlast ? off : 0u);
+          } else {
+            raw[g][u] = chain_pack_tab(ht.tab, h32(base + rel) & ht.mask);
+          }
+        }
+      }
+    }
+    chain_hist_zero(lds, nkeys);
+    chain_wave_sync();
+    chain_pack_add(lds, rw[0]);
+    chain_pack_add(lds, rw[1]);
+    // a longer window is streamed
+    for (uint32_t c = kPackPreChunks + lane; c < chunks; c += kChainWave)
+      chain_pack_add(lds, rows[c]);
+    chain_wave_sync();
+    int64_t left = m - t * kChainTile;
+    if (__builtin_expect(left >= kChainTile, 1))
+      acc += chain_packed_finish<kKind, false>(lds, p, raw, ht, base, shift,
+                                               bits, kChainTile);
+    else
+      acc += chain_packed_finish<kKind, true>(lds, p, raw, ht, base, shift,
+                                              bits,
+                                              static_cast<uint32_t>(left));
+    chain_wave_sync();  // before the next tile refills the slice
+  }
+  return acc;
+}
+
+// The direct-count tier of chain_count_kernel over packed tiles: the same
+// wave-owned 1024-seed tile, resident grid, 8 KB slice and partial sums,
+// with 4 dwordx4 of seeds and 2 of rows per lane.
+__global__ void __launch_bounds__(kChainWave, 4)
+chain_count_packed_kernel(const uint4* __restrict__ pseeds,
+                          const uint4* __restrict__ prows,
+                          const uint4* __restrict__ recs, int64_t m,
+                          int64_t n_tiles, ChainPackedHt ht,
+                          unsigned long long* __restrict__ parts,
+                          int n_parts) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kChainSpan + kChainPad];
+  unsigned long long acc;
+  if (ht.kind == kPackHtDirect)
+    acc = chain_packed_tiles<kPackHtDirect>(lds, pseeds, prows, recs, m,
+                                            n_tiles, ht);
+  else if (ht.kind == kPackHtTable32)
+    acc = chain_packed_tiles<kPackHtTable32>(lds, pseeds, prows, recs, m,
+                                             n_tiles, ht);
+  else
+    acc = chain_packed_tiles<kPackHtNone>(lds, pseeds, prows, recs, m,
+                                          n_tiles, ht);
+  for (int off = 32; off > 0; off >>= 1)
+    acc += __shfl_down(acc, off);
+  if (threadIdx.x == 0 && acc)
+    atomicAdd(parts + (blockIdx.x % n_parts) * kChainPartStride, acc);
 }
 
 // KOLIBRIE_CHAIN_GRID caps the chain kernel's grid in place of the default
@@ -1870,28 +2190,36 @@ inline int64_t chain_grid_cap() {
 // the runtime, since it follows the kernel's registers and LDS); the rest
 // grid-stride.  All waves start together, so none queues behind a full
 // first round.  A wave per tile measured the same (round 4).
-inline int chain_grid(int64_t n_tiles, int64_t cap) {
-  static const int resident = [] {
-    int per_cu = 0, dev = 0, cus = 0;
-    HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, chain_count_kernel, kChainWave, 0));
-    HIP_OK(hipGetDevice(&dev));
-    HIP_OK(hipDeviceGetAttribute(
-        &cus, hipDeviceAttributeMultiprocessorCount, dev));
-    return std::max(1, per_cu * cus);
-  }();
-  int64_t grid = std::min<int64_t>(n_tiles, cap > 0 ? cap : resident);
+template <class Kernel>
+inline int chain_resident(Kernel kernel) {
+  int per_cu = 0, dev = 0, cus = 0;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &per_cu, kernel, kChainWave, 0));
+  HIP_OK(hipGetDevice(&dev));
+  HIP_OK(hipDeviceGetAttribute(
+      &cus, hipDeviceAttributeMultiprocessorCount, dev));
+  return std::max(1, per_cu * cus);
+}
+
+inline int chain_grid(int64_t n_tiles, int64_t cap, bool packed = false) {
+  static const int resident = chain_resident(chain_count_kernel);
+  static const int resident_packed =
+      chain_resident(chain_count_packed_kernel);
+  int64_t grid = std::min<int64_t>(
+      n_tiles, cap > 0 ? cap : packed ? resident_packed : resident);
   return static_cast<int>(std::max<int64_t>(1, grid));
 }
 
 // the chain kernel into `parts` (kChainParts zeroed partial sums) and their
 // sum into *total; with parts == nullptr every wave adds to *total itself
-// (a caller that brings no scratch), which must then be zero beforehand
+// (a caller that brings no scratch), which must then be zero beforehand;
+// with host_out the sum and a flag go to that host-mapped address instead
 inline void chain_launch(const int32_t* seed_b, const int32_t* seed_z,
                          int64_t m, const ChainHops& hops,
                          const int64_t* win, unsigned long long* parts,
                          unsigned long long* total, int64_t n_tiles,
-                         int64_t grid_cap, hipStream_t stream) {
+                         int64_t grid_cap, hipStream_t stream,
+                         unsigned long long* host_out = nullptr) {
   hipLaunchKernelGGL(chain_count_kernel,
                      dim3(chain_grid(n_tiles, grid_cap)), dim3(kChainWave),
                      0, stream, seed_b, seed_z, m, hops, win,
@@ -1899,7 +2227,7 @@ inline void chain_launch(const int32_t* seed_b, const int32_t* seed_z,
   HIP_OK(hipGetLastError());
   if (parts) {
     hipLaunchKernelGGL(chain_total_kernel, dim3(1), dim3(kChainParts), 0,
-                       stream, parts, total);
+                       stream, parts, total, host_out);
     HIP_OK(hipGetLastError());
   }
 }
@@ -1998,22 +2326,120 @@ void chain_count_into(at::Tensor seed_b, at::Tensor seed_z,
 
 // ---- C++ serving path (crush the per-query host
 // floor).  All launch arguments for a cached COUNT chain live in a
-// C++-side registry; one pybind call then does: zero the accumulator,
-// two direct kernel launches, an 8-byte D2H into pinned memory and a
-// stream sync — no Python plan walk, no torch dispatcher, no graph
-// replay floor (direct launches are ~3-4 µs each vs 10-16 µs replay,
-// MI355X guide §graph-replay-floor).
+// C++-side registry; one pybind call then does two direct kernel launches,
+// the second of which stores the count and a flag into host-mapped pinned
+// memory, and a spin on that flag — no Python plan walk, no torch
+// dispatcher, no copy command, no graph replay floor (direct launches are
+// ~3-4 µs each vs 10-16 µs replay, MI355X guide §graph-replay-floor).
 struct ChainServe {
   at::Tensor seed_b, seed_z, win, total;
+  // packed tiles (see chain_pack_tiles_kernel): they replace seed_b, seed_z
+  // and win when the registration qualifies
+  at::Tensor pseeds, prows, recs;
+  ChainPackedHt pht{};
+  bool packed = false;
   std::vector<at::Tensor> keep;
   ChainHops hops{};
   int64_t m = 0, n_tiles = 0, grid_cap = 0;
+  // 16 host-mapped bytes, {count, flag}, and their device address
   int64_t* pinned = nullptr;
+  unsigned long long* pinned_dev = nullptr;
   ~ChainServe() {
     if (pinned) (void)hipHostFree(pinned);
   }
 };
 static std::vector<std::unique_ptr<ChainServe>> g_chain_serves;
+
+// Decide once whether the registration takes the packed tiles (the rule is
+// stated at chain_pack_rule_kernel) and build them if so.  cs.win holds the
+// windows already.  One host sync.
+static void chain_try_pack(ChainServe& cs, const at::Tensor& seed_b,
+                           const at::Tensor& seed_z,
+                           const std::vector<at::Tensor>& hop_key32,
+                           hipStream_t stream) {
+  const char* env = getenv("KOLIBRIE_CHAIN_PACKED");
+  if (env && atoi(env) == 0) return;
+  const ChainHops& hops = cs.hops;
+  int hp = -1, ht = -1;
+  for (int h = 0; h < hops.k; ++h) {
+    bool probe32 = hops.direct[h] != nullptr || hops.table32[h] != nullptr;
+    if (probe32 && ht < 0) {
+      ht = h;
+    } else if (!probe32 && hops.table[h] == nullptr && hops.src[h] == 0
+               && hp < 0) {
+      hp = h;
+    } else {
+      return;  // a third hop, a u64 table, a src-1 search, a second of a kind
+    }
+  }
+  if (hp < 0) return;
+  ChainPackedHt pht{};
+  bool use_z = false;
+  if (ht >= 0) {
+    pht.src = static_cast<uint32_t>(hops.src[ht]);
+    use_z = hops.src[ht] != 0;
+    constexpr int64_t kSlots = int64_t{1} << 30;
+    if (hops.direct[ht] != nullptr) {
+      if (hops.dlen[ht] > kSlots
+          || hops.dmin[ht] + hops.dlen[ht] > (int64_t{1} << 32))
+        return;
+      pht.kind = kPackHtDirect;
+      pht.tab = hops.direct[ht];
+      pht.dmin = static_cast<uint32_t>(hops.dmin[ht]);
+      pht.dlast = static_cast<uint32_t>(hops.dlen[ht] - 1);
+    } else {
+      if (hops.tmask[ht] >= kSlots) return;
+      pht.kind = kPackHtTable32;
+      pht.tab = hops.table32[ht];
+      pht.mask = static_cast<uint32_t>(hops.tmask[ht]);
+    }
+  }
+  auto opts = seed_b.options().dtype(at::kLong);
+  auto stats = at::zeros({kPackStats}, opts);
+  auto chunks = at::empty({cs.n_tiles}, opts);
+  auto* stats_u = reinterpret_cast<unsigned long long*>(
+      stats.data_ptr<int64_t>());
+  hipLaunchKernelGGL(chain_pack_rule_kernel, dim3(grid_for(cs.n_tiles)),
+                     dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
+                     cs.m, cs.n_tiles, cs.win.data_ptr<int64_t>(), hops.k, hp,
+                     hops.lds_min, chunks.data_ptr<int64_t>(), stats_u);
+  HIP_OK(hipGetLastError());
+  if (use_z) {
+    hipLaunchKernelGGL(chain_pack_zrange_kernel, dim3(grid_for(cs.m)),
+                       dim3(kBlock), 0, stream, seed_z.data_ptr<int32_t>(),
+                       cs.m, stats_u);
+    HIP_OK(hipGetLastError());
+  }
+  auto offs = at::cumsum(chunks, 0);
+  auto host = at::cat({stats, offs.slice(0, cs.n_tiles - 1)}).cpu();
+  const int64_t* st = host.data_ptr<int64_t>();
+  const int64_t total_chunks = st[kPackStats];
+  const uint32_t zmin = ~static_cast<uint32_t>(st[kPackZMaxInv]);
+  const uint32_t zmax = static_cast<uint32_t>(st[kPackZMax]);
+  if (st[kPackBad] != 0) return;
+  if (use_z && zmax - zmin >= (1u << kPackZBits)) return;
+  if (st[kPackRows] > 2 * (cs.m + hops.n[hp])) return;
+  if (total_chunks > 0xFFFFFFFFll) return;
+  pht.zmin = use_z ? zmin : 0u;
+  cs.pseeds = at::empty({cs.n_tiles * kChainTile},
+                        seed_b.options().dtype(at::kInt));
+  cs.prows = at::empty({std::max<int64_t>(1, total_chunks) * kPackChunk},
+                       seed_b.options().dtype(at::kShort));
+  cs.recs = at::empty({cs.n_tiles * 4}, seed_b.options().dtype(at::kInt));
+  hipLaunchKernelGGL(
+      chain_pack_tiles_kernel,
+      dim3(static_cast<int>(std::min<int64_t>(cs.n_tiles, 65536))),
+      dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
+      seed_z.data_ptr<int32_t>(), cs.m, cs.n_tiles,
+      hop_key32[hp].data_ptr<int32_t>(), cs.win.data_ptr<int64_t>(), hops.k,
+      hp, offs.data_ptr<int64_t>(), pht.zmin, use_z,
+      reinterpret_cast<uint32_t*>(cs.pseeds.data_ptr<int32_t>()),
+      reinterpret_cast<uint16_t*>(cs.prows.data_ptr<int16_t>()),
+      reinterpret_cast<uint4*>(cs.recs.data_ptr<int32_t>()));
+  HIP_OK(hipGetLastError());
+  cs.pht = pht;
+  cs.packed = true;
+}
 
 int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
                              std::vector<at::Tensor> hop_key32,
@@ -2024,16 +2450,6 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
               && seed_z.is_cuda());
   auto cs = std::make_unique<ChainServe>();
   cs->hops = chain_hops_from(hop_key32, hop_src, hop_table, hop_dmin);
-  // the kernel reads each seed column with dwordx4 when its pointer is
-  // 16-byte aligned; seed_z usually arrives as a slice of the PSO column,
-  // aligned to 4 bytes only.  The seeds are immutable for this
-  // registration's lifetime, so take an aligned copy once here.
-  auto aligned16 = [](const at::Tensor& x) {
-    bool ok = reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0;
-    return ok ? x : x.clone();
-  };
-  cs->seed_b = aligned16(seed_b);
-  cs->seed_z = aligned16(seed_z);
   cs->m = seed_b.numel();
   cs->grid_cap = chain_grid_cap();
   // the hops point into these tensors
@@ -2042,25 +2458,43 @@ int64_t register_chain_serve(at::Tensor seed_b, at::Tensor seed_z,
   cs->n_tiles = (cs->m + kChainTile - 1) / kChainTile;
   cs->win = at::empty({std::max<int64_t>(1, cs->n_tiles * cs->hops.k * 2)},
                       seed_b.options().dtype(at::kLong));
-  // total[0] = the count, total[1] = constant 1 (the completion flag's
-  // device source: same-stream copies are ordered, so once the flag
-  // lands in pinned memory the count before it is valid); behind them,
-  // from a 128-byte boundary, the partial sums
+  // total[0] = the count where no host address is given; behind it, from a
+  // 128-byte boundary, the partial sums
   cs->total = at::zeros({kChainPartStride + kChainParts * kChainPartStride},
                         seed_b.options().dtype(at::kLong));
-  cs->total[1] = 1;
-  HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&cs->pinned), 16));
+  // the count and the completion flag are stored by chain_total_kernel
+  // itself: coherent host memory that the device addresses
+  HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&cs->pinned), 16,
+                       hipHostMallocMapped | hipHostMallocCoherent));
+  HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&cs->pinned_dev),
+                                 cs->pinned, 0));
+  cs->pinned[0] = cs->pinned[1] = 0;
   // the per-tile hop windows depend only on the CACHED seeds + hop
   // regions (immutable for this registration's lifetime: a store-version
   // bump re-registers), so compute them ONCE here instead of per query —
   // chain_tile_bounds was ~8% of the serve step.  It also zeroes the
   // accumulator, so the first serve call starts clean.
   if (cs->m > 0) {
-    chain_bounds_launch(cs->seed_b.data_ptr<int32_t>(), cs->m, cs->n_tiles,
+    chain_bounds_launch(seed_b.data_ptr<int32_t>(), cs->m, cs->n_tiles,
                         cs->hops, cs->win.data_ptr<int64_t>(),
                         reinterpret_cast<unsigned long long*>(
                             cs->total.data_ptr<int64_t>()),
                         cur_stream());
+    chain_try_pack(*cs, seed_b, seed_z, hop_key32, cur_stream());
+  }
+  if (cs->packed) {
+    cs->win = at::Tensor();  // the records hold what the kernel needs of it
+  } else {
+    // the kernel reads each seed column with dwordx4 when its pointer is
+    // 16-byte aligned; seed_z usually arrives as a slice of the PSO column,
+    // aligned to 4 bytes only.  The seeds are immutable for this
+    // registration's lifetime, so take an aligned copy once here.
+    auto aligned16 = [](const at::Tensor& x) {
+      bool ok = reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0;
+      return ok ? x : x.clone();
+    };
+    cs->seed_b = aligned16(seed_b);
+    cs->seed_z = aligned16(seed_z);
   }
   g_chain_serves.push_back(std::move(cs));
   return static_cast<int64_t>(g_chain_serves.size() - 1);
@@ -2077,15 +2511,29 @@ int64_t serve_chain_count(int64_t id) {
   // there (first call) or by chain_total_kernel in the previous call
   unsigned long long* total_u =
       reinterpret_cast<unsigned long long*>(total_ptr);
-  chain_launch(cs.seed_b.data_ptr<int32_t>(), cs.seed_z.data_ptr<int32_t>(),
-               cs.m, cs.hops, cs.win.data_ptr<int64_t>(),
-               total_u + kChainPartStride, total_u, cs.n_tiles, cs.grid_cap,
-               stream);
-  HIP_OK(hipMemcpyAsync(cs.pinned, total_ptr, 16, hipMemcpyDeviceToHost,
-                        stream));
-  // spin on the pinned flag: hipStreamSynchronize pays tens of µs of
-  // scheduler yield latency, the DMA lands in ~µs.  Bounded: fall back
-  // to a real sync after ~2e9 spins (GPU hung elsewhere).
+  if (cs.packed) {
+    hipLaunchKernelGGL(
+        chain_count_packed_kernel,
+        dim3(chain_grid(cs.n_tiles, cs.grid_cap, true)), dim3(kChainWave), 0,
+        stream, reinterpret_cast<const uint4*>(cs.pseeds.data_ptr<int32_t>()),
+        reinterpret_cast<const uint4*>(cs.prows.data_ptr<int16_t>()),
+        reinterpret_cast<const uint4*>(cs.recs.data_ptr<int32_t>()), cs.m,
+        cs.n_tiles, cs.pht, total_u + kChainPartStride, kChainParts);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(chain_total_kernel, dim3(1), dim3(kChainParts), 0,
+                       stream, total_u + kChainPartStride, total_u,
+                       cs.pinned_dev);
+    HIP_OK(hipGetLastError());
+  } else {
+    chain_launch(cs.seed_b.data_ptr<int32_t>(),
+                 cs.seed_z.data_ptr<int32_t>(), cs.m, cs.hops,
+                 cs.win.data_ptr<int64_t>(), total_u + kChainPartStride,
+                 total_u, cs.n_tiles, cs.grid_cap, stream, cs.pinned_dev);
+  }
+  // spin on the pinned flag, which chain_total_kernel stores after the
+  // count: hipStreamSynchronize pays tens of µs of scheduler yield
+  // latency.  Bounded: fall back to a real sync after ~2e9 spins (GPU
+  // hung elsewhere).
   for (int64_t spins = 0; *flag == 0; ++spins) {
 #if defined(__x86_64__)
     __builtin_ia32_pause();
@@ -2095,7 +2543,14 @@ int64_t serve_chain_count(int64_t id) {
       break;
     }
   }
-  return cs.pinned[0];
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);  // the count is read after the flag
+  return *static_cast<volatile int64_t*>(cs.pinned);
+}
+
+bool chain_serve_packed(int64_t id) {
+  const auto& cs = g_chain_serves.at(id);
+  TORCH_CHECK(cs != nullptr, "chain serve handle ", id, " was released");
+  return cs->packed;
 }
 
 void release_chain_serve(int64_t id) {
@@ -4508,6 +4963,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("serve_chain_count", &serve_chain_count,
         py::call_guard<py::gil_scoped_release>(),
         "one-call serving: direct launches + pinned 8-byte readback");
+  m.def("chain_serve_packed", &chain_serve_packed,
+        "whether a serve handle took the packed-tile format (6 B per seed)");
   m.def("release_chain_serve", &release_chain_serve,
         "drop a cached serve handle (store changed)");
   m.def("build_count_table32", &build_count_table32,
