@@ -9,6 +9,10 @@ _COUNTERS: Dict[str, int] = {
     "SCAN_PROBES": 0,
     "QUADS_EXAMINED": 0,
     "ROWS_EMITTED": 0,
+    # bound-endpoint property paths (engine/paths.py): BFS sources run and
+    # BFS levels that found a non-empty frontier
+    "PATH_REACH_SOURCES": 0,
+    "PATH_REACH_LEVELS": 0,
 }
 
 enabled = True

@@ -593,7 +593,10 @@ class ExecutionEngine:
             return self._scan_index(idx, pattern, incoming, extra=None,
                                     needed=needed, sort_hint=sort_hint)
         if scope[0] == "closure":
-            idx = self._closure_index(scope[1], scope[2], scope[3])
+            out = self._closure_reach(pattern, scope, incoming, needed)
+            if out is not None:
+                return out
+            idx = self._closure_index(scope[1], scope[2], scope[3], scope[4])
             return self._scan_index(idx, pattern, incoming, extra=None,
                                     needed=needed, sort_hint=sort_hint)
         # GRAPH ?g — iterate named graphs, bind the graph variable
@@ -612,31 +615,129 @@ class ExecutionEngine:
             return Bindings.empty(self.device, all_vars)
         return Bindings.concat(parts, self.device)
 
-    def _closure_index(self, pid: int, reflexive: bool,
-                       gid: Optional[int] = None) -> GraphIndex:
-        """Transitive closure of predicate `pid` as an auxiliary
-        GraphIndex, materialized by log-doubling joins on device and
-        cached per store version (p+ / p* property paths).  `*` adds the
-        zero-length pairs over the predicate's node set."""
+    def _closure_graph_key(self, gid: Optional[int]):
+        """Graph part of the path caches' keys: a named graph's id, or the
+        dataset view's default graphs."""
+        if gid is not None:
+            return gid
+        gs = tuple(self.ctx.view.default_graphs)
+        return None if gs == (DEFAULT_GRAPH,) else gs
+
+    def _closure_reach(self, pattern: TriplePattern, scope,
+                       incoming: Bindings, needed) -> Optional[Bindings]:
+        """A closure step with a bound endpoint, answered by reachability
+        from the distinct bound values (engine/paths.py: the K12 kernel on
+        a GPU) instead of the whole closure.  None sends the step to the
+        closure index: no endpoint bound, UNBOUND cells possible, too many
+        sources, the index already cached, KOLIBRIE_PATH_REACH=0, or a
+        distributed plan."""
+        from . import paths
+        if not paths.enabled() or self.ctx.world != 1:
+            return None
+        _tag, pids, reflexive, gid, max_hops = scope
+        s_t, o_t = pattern.s, pattern.o
+        if not all(isinstance(t, (Constant, Variable)) for t in (s_t, o_t)):
+            return None
+        is_unit = incoming.n == 1 and not incoming.cols
+
+        def bound(t) -> bool:
+            return isinstance(t, Constant) or (not is_unit
+                                               and incoming.has(t.name))
+        if bound(s_t):
+            src_t, far_t, inverse = s_t, o_t, False
+        elif bound(o_t):
+            src_t, far_t, inverse = o_t, s_t, True
+        else:
+            return None
+        if incoming.maybe_unbound and any(
+                isinstance(t, Variable) and incoming.has(t.name)
+                for t in (s_t, o_t)):
+            return None           # UNBOUND endpoints: the probe path's rules
+        hit = getattr(self.db, "_closures", {}).get(
+            (pids, reflexive, gid, max_hops))
+        if hit is not None and hit[0] == self.db.store.version:
+            return None           # probing the cached index is cheaper
+        dev = self.device
+        if isinstance(src_t, Constant):
+            sources = torch.tensor([src_t.id], dtype=torch.int32, device=dev)
+            row_src = None
+        else:
+            sources, row_src = torch.unique(incoming.col(src_t.name),
+                                            return_inverse=True)
+        if sources.numel() > paths.max_sources():
+            return None
+        gkey = self._closure_graph_key(gid)
+        same_var = (isinstance(far_t, Variable) and isinstance(src_t, Variable)
+                    and far_t.name == src_t.name)
+        if (needed is not None and not needed and not same_var
+                and not bound(far_t)):
+            # COUNT(*) pushdown: per-source reach counts, summed over rows
+            counts = paths.reach(self.db, sources, pids, inverse=inverse,
+                                 reflexive=reflexive, max_hops=max_hops,
+                                 gid=gkey, count_only=True)
+            total = int(counts.sum().item()) * incoming.n if row_src is None \
+                else int(counts[row_src].sum().item())
+            exec_stats.bump("ROWS_EMITTED", total)
+            return Bindings({}, total, dev)
+        pos, nodes = paths.reach(self.db, sources, pids, inverse=inverse,
+                                 reflexive=reflexive, max_hops=max_hops,
+                                 gid=gkey)
+        src_ids = sources[pos]
+        keep = None
+        if isinstance(far_t, Constant):
+            keep = nodes == far_t.id
+        elif same_var:
+            keep = nodes == src_ids
+        if keep is not None:
+            src_ids, nodes = src_ids[keep], nodes[keep]
+        cols: Dict[str, torch.Tensor] = {}
+        if isinstance(src_t, Variable):
+            cols[src_t.name] = src_ids
+        if isinstance(far_t, Variable) and not same_var:
+            cols[far_t.name] = nodes
+        cand = Bindings(cols, int(nodes.numel()), dev)
+        exec_stats.bump("QUADS_EXAMINED", cand.n)
+        if is_unit:
+            out = _prune(cand, needed)
+        else:
+            keep_vars = None if needed is None else set(needed) | set(cols)
+            out = join_bindings(_prune(incoming, keep_vars), cand, needed)
+        exec_stats.bump("ROWS_EMITTED", out.n)
+        return out
+
+    def _closure_index(self, pids, reflexive: bool,
+                       gid: Optional[int] = None,
+                       max_hops: Optional[int] = None) -> GraphIndex:
+        """Transitive closure of the union of predicates `pids` as an
+        auxiliary GraphIndex, materialized by log-doubling joins on device
+        and cached per store version (p+ / p* property paths).  `*` adds
+        the zero-length pairs over the predicates' node set; a hop bound of
+        1 (`?`) keeps the direct edges.  The index carries the first
+        predicate id in its p column."""
+        if isinstance(pids, int):
+            pids = (pids & 0xFFFFFFFF,)
+        if max_hops not in (None, 1):
+            raise ValueError("closure index supports no hop bound but 1")
         cache = getattr(self.db, "_closures", None)
         if cache is None:
             cache = self.db._closures = {}
-        key = (pid, reflexive, gid)
+        key = (tuple(pids), reflexive, gid, max_hops)
         hit = cache.get(key)
         if hit is not None and hit[0] == self.db.store.version:
             return hit[1]
-        from .scan import scan_unit
-        from .tensor_utils import pack2, unique_rows
+        from .paths import predicate_edges
+        from .tensor_utils import unique_rows
+        pid = pids[0]
         pid_i32 = pid - 0x1_0000_0000 if pid >= 0x8000_0000 else pid
         base = self.ctx.default_index() if gid is None \
             else self.db.store.graph_index(gid)
-        s, _p, o = scan_unit(base, {1: pid_i32})
+        s, o = predicate_edges(base, pids)
         dev = self.device
         cs, co = s, o
         # squaring: C_{k+1} = C_k ∪ (C_k ∘ C_k) reaches length 2^k in k
         # rounds (log-depth for chains; joins are the same sorted
         # searchsorted machinery as the fixpoint kernels drive)
-        for _ in range(64):
+        for _ in range(64 if max_hops is None else 0):
             cs, co = unique_rows([cs, co])
             # join C.o == C.s
             left_o = co.to(torch.int64) & 0xFFFFFFFF
@@ -660,6 +761,8 @@ class ExecutionEngine:
                 cs, co = u_s, u_o
                 break
             cs, co = u_s, u_o
+        if max_hops is not None:
+            cs, co = unique_rows([cs, co])
         if reflexive:
             nodes = torch.unique(torch.cat([s, o]))
             cs = torch.cat([cs, nodes])

@@ -17,6 +17,9 @@
 //                    skip and numeric classification over the term-text
 //                    table (replaces the per-row decode + sorted() of
 //                    execute_query.rs:477's port).
+//   K12 path_reach — property paths from a bound endpoint: multi-source
+//                    level-synchronous BFS over a CSR adjacency, 64 sources
+//                    per pass as the bits of per-node uint64 masks.
 //
 // Design notes (per CDNA4 guide): wave64, 256-thread blocks, grid-stride
 // loops capped so the 256-CU chip is saturated without oversubscription;
@@ -877,6 +880,226 @@ __global__ void term_numeric_class_kernel(const int32_t* __restrict__ ids,
     }
     bool accept = st == NS_INT || st == NS_FRAC || st == NS_EXP;
     out[i] = forbidden ? 0 : accept ? 1 : 2;
+  }
+}
+
+// ------------------------------------------------------ K12 path_reach kernels
+// Reachability from up to 64 sources at once over a CSR adjacency of compact
+// node ids (p+ / p* / p? from a bound endpoint).  Source k of a pass owns bit
+// k of three per-node uint64 masks: `seen` (reached by a path of >= 1 edge),
+// `cur` (this level's frontier) and `nxt` (the next one).  Sources are NOT
+// pre-marked in seen, so a source reaches itself only round a cycle.
+//
+// One launch is one BFS level over a node-id work queue whose length lives in
+// device memory; the grid is fixed and strides over that length, so a level
+// on an empty queue is a no-op and the host may launch several levels back to
+// back before it reads the length once.  Words of the pass state:
+//   [0..2] queue lengths in rotation: level k reads [k%3], appends to
+//          [(k+1)%3] and zeroes [(k+2)%3] (last level's input, next level's
+//          output: no block touches it during level k)
+//   [3]    levels that found a non-empty queue
+//   [4]    appends refused because the queue was full (never, by the
+//          once-per-level rule below; the host raises if it is not 0)
+// Blocks of one launch share data only through atomics: seen/nxt take
+// agent-scope 64-bit ORs, the queue length an add.  The plain load of
+// seen[w] in front of the OR is a filter only: an L1/L2 copy can be stale
+// towards FEWER bits (bits are only ever added inside a pass), which costs a
+// redundant atomic and never loses one.  A node enters the next queue only
+// when nxt[w] was 0 before the OR, so at most once per level: n_nodes
+// entries suffice.  cur[v] is cleared by the one lane that owns queue entry
+// v, so the array is all zero when it becomes `nxt` two levels on.
+constexpr int kReachBlock = 256;
+constexpr int kReachGrid = 1024;       // 4 blocks per CU, strides the queue
+constexpr int kReachStateWords = 8;
+constexpr int kReachBatch = 64;        // sources per pass = mask bits
+
+__device__ __forceinline__ uint64_t reach_shfl64(uint64_t x, int src) {
+  uint32_t lo = __shfl(static_cast<uint32_t>(x), src);
+  uint32_t hi = __shfl(static_cast<uint32_t>(x >> 32), src);
+  return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
+// offer mask m to neighbour w; true when w must join the next queue
+__device__ __forceinline__ bool reach_visit(
+    int32_t w, uint64_t m, int32_t n_nodes,
+    unsigned long long* __restrict__ seen,
+    unsigned long long* __restrict__ nxt) {
+  if (static_cast<uint32_t>(w) >= static_cast<uint32_t>(n_nodes)) return false;
+  uint64_t d = m & ~seen[w];
+  if (d == 0) return false;
+  d &= ~atomicOr(&seen[w], d);
+  if (d == 0) return false;
+  return atomicOr(&nxt[w], d) == 0;
+}
+
+// wave-aggregated queue append (guide G12): one add per wave instruction.
+// Must be reached by all 64 lanes.
+__device__ __forceinline__ void reach_push(bool push, int32_t w, int lane,
+                                           int32_t* __restrict__ q_out,
+                                           uint32_t* len_out, uint32_t cap,
+                                           uint32_t* refused) {
+  const uint64_t b = __ballot(push);
+  if (b == 0) return;
+  const int leader = __ffsll(static_cast<unsigned long long>(b)) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(len_out, static_cast<uint32_t>(__popcll(b)));
+  base = __shfl(base, leader);
+  if (push) {
+    uint32_t pos = base + __popcll(b & ((1ull << lane) - 1ull));
+    if (pos < cap) q_out[pos] = w;
+    else atomicAdd(refused, 1u);
+  }
+}
+
+__global__ void path_reach_seed(const int32_t* __restrict__ sources, int n_src,
+                                int32_t n_nodes,
+                                unsigned long long* __restrict__ cur,
+                                int32_t* __restrict__ queue,
+                                uint32_t* __restrict__ state) {
+  const int k = threadIdx.x;
+  if (k >= n_src) return;
+  const int32_t v = sources[k];
+  if (static_cast<uint32_t>(v) >= static_cast<uint32_t>(n_nodes)) return;
+  // the same node may be the source of several bits: queue it once
+  if (atomicOr(&cur[v], 1ull << k) == 0) {
+    uint32_t pos = atomicAdd(&state[0], 1u);
+    queue[pos] = v;                     // pos < n_src <= 64 <= queue capacity
+  }
+}
+
+__global__ void __launch_bounds__(kReachBlock)
+path_reach_level(const int32_t* __restrict__ row_ptr,
+                 const int32_t* __restrict__ col, int32_t n_nodes,
+                 unsigned long long* __restrict__ seen,
+                 unsigned long long* __restrict__ cur,
+                 unsigned long long* __restrict__ nxt,
+                 const int32_t* __restrict__ q_in, int32_t* __restrict__ q_out,
+                 uint32_t* state, int slot, int hub_degree) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t len_in = state[slot];
+  uint32_t* len_out = &state[(slot + 1) % 3];
+  uint32_t* refused = &state[4];
+  const uint32_t cap = static_cast<uint32_t>(n_nodes);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    state[(slot + 2) % 3] = 0;
+    if (len_in != 0) state[3] += 1;
+  }
+  const uint32_t wave = (blockIdx.x * kReachBlock + threadIdx.x) >> 6;
+  const uint32_t n_waves = gridDim.x * (kReachBlock >> 6);
+  // A wave takes `chunk` consecutive entries per trip: 64 when the queue
+  // fills the grid, fewer when it is short, so that the entries of a short
+  // queue (64 hubs, say) go to as many waves instead of queueing up in one.
+  // Wave-uniform trip count: the ballots below need all 64 lanes.
+  uint32_t chunk = (len_in + n_waves - 1) / n_waves;
+  chunk = chunk < 1 ? 1 : chunk > 64 ? 64 : chunk;
+  for (uint64_t base = static_cast<uint64_t>(wave) * chunk; base < len_in;
+       base += static_cast<uint64_t>(n_waves) * chunk) {
+    const uint64_t i = base + lane;
+    const bool act = static_cast<uint32_t>(lane) < chunk && i < len_in;
+    uint64_t m = 0;
+    int32_t rs = 0, re = 0;
+    if (act) {
+      const int32_t v = q_in[i];
+      if (static_cast<uint32_t>(v) < cap) {
+        m = cur[v];
+        cur[v] = 0;
+        rs = row_ptr[v];
+        re = row_ptr[v + 1];
+      }
+    }
+    const int deg = re - rs;
+    const bool hub = deg >= hub_degree;
+    // tier 1: a lane walks its own short neighbour list
+    const int mine = hub ? 0 : deg;
+    for (int j = 0; __any(j < mine); ++j) {
+      bool push = false;
+      int32_t w = 0;
+      if (j < mine) {
+        w = col[rs + j];
+        push = reach_visit(w, m, n_nodes, seen, nxt);
+      }
+      reach_push(push, w, lane, q_out, len_out, cap, refused);
+    }
+    // tier 2: the wave walks each long list together, coalesced col reads
+    uint64_t hubs = __ballot(hub);
+    while (hubs != 0) {
+      const int src = __ffsll(static_cast<unsigned long long>(hubs)) - 1;
+      hubs &= hubs - 1;
+      const int64_t hs = __shfl(rs, src);
+      const int64_t he = __shfl(re, src);
+      const uint64_t hm = reach_shfl64(m, src);
+      for (int64_t e = hs; e < he; e += 64) {
+        const int64_t idx = e + lane;
+        bool push = false;
+        int32_t w = 0;
+        if (idx < he) {
+          w = col[idx];
+          push = reach_visit(w, hm, n_nodes, seen, nxt);
+        }
+        reach_push(push, w, lane, q_out, len_out, cap, refused);
+      }
+    }
+  }
+}
+
+// Per node the number of sources that reached it, and per source (bit) the
+// number of nodes it reached: lane k sums bit k, one add per lane and wave.
+__global__ void __launch_bounds__(kReachBlock)
+path_reach_count(const unsigned long long* __restrict__ seen, int32_t n_nodes,
+                 int32_t* __restrict__ node_count,
+                 unsigned long long* __restrict__ per_source) {
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = (blockIdx.x * kReachBlock + threadIdx.x) >> 6;
+  const uint32_t n_waves = gridDim.x * (kReachBlock >> 6);
+  unsigned long long acc = 0;
+  for (int64_t base = static_cast<int64_t>(wave) * 64; base < n_nodes;
+       base += static_cast<int64_t>(n_waves) * 64) {
+    const int64_t v = base + lane;
+    const uint64_t m = v < n_nodes ? seen[v] : 0;
+    if (v < n_nodes && node_count != nullptr) node_count[v] = __popcll(m);
+    if (__ballot(m != 0) == 0) continue;
+    for (int k = 0; k < 64; ++k) {
+      const uint64_t b = __ballot((m >> k) & 1);
+      if (lane == k) acc += __popcll(b);
+    }
+  }
+  if (acc != 0) atomicAdd(&per_source[lane], acc);
+}
+
+// did source k reach itself (it lies on a cycle)?
+__global__ void path_reach_self(const int32_t* __restrict__ sources, int n_src,
+                                int32_t n_nodes,
+                                const unsigned long long* __restrict__ seen,
+                                uint8_t* __restrict__ self_hit) {
+  const int k = threadIdx.x;
+  if (k >= n_src) return;
+  const int32_t v = sources[k];
+  bool hit = false;
+  if (static_cast<uint32_t>(v) < static_cast<uint32_t>(n_nodes))
+    hit = (seen[v] >> k) & 1;
+  self_hit[k] = hit ? 1 : 0;
+}
+
+// (source position, node) per set bit, at the node's exclusive-scan offset
+__global__ void __launch_bounds__(kReachBlock)
+path_reach_emit(const unsigned long long* __restrict__ seen, int32_t n_nodes,
+                const int64_t* __restrict__ offset_incl,
+                int32_t pos_base, int64_t total,
+                int32_t* __restrict__ out_pos, int32_t* __restrict__ out_node) {
+  for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < n_nodes;
+       v += (int64_t)gridDim.x * blockDim.x) {
+    uint64_t m = seen[v];
+    if (m == 0) continue;
+    int64_t at = offset_incl[v] - __popcll(m);
+    while (m != 0) {
+      const int k = __ffsll(static_cast<unsigned long long>(m)) - 1;
+      m &= m - 1;
+      if (at >= 0 && at < total) {
+        out_pos[at] = pos_base + k;
+        out_node[at] = static_cast<int32_t>(v);
+      }
+      ++at;
+    }
   }
 }
 
@@ -3058,6 +3281,179 @@ at::Tensor term_numeric_class(at::Tensor ids, at::Tensor bytes,
   return out;
 }
 
+// K12 path_reach wrapper.  Every argument is checked on the host before the
+// first launch: dtypes, device, contiguity, the CSR's shape and the value
+// ranges of col and sources (one small read-back per call).
+static void path_reach_check(const at::Tensor& row_ptr, const at::Tensor& col,
+                             const at::Tensor& sources, int64_t max_hops,
+                             int64_t levels_per_sync, int64_t hub_degree) {
+  const char* who = "path_reach";
+  TORCH_CHECK(row_ptr.is_cuda() && row_ptr.dtype() == at::kInt
+              && row_ptr.dim() == 1 && row_ptr.is_contiguous(),
+              who, ": row_ptr must be int32 on device");
+  TORCH_CHECK(col.is_cuda() && col.dtype() == at::kInt && col.dim() == 1
+              && col.is_contiguous(), who, ": col must be int32 on device");
+  TORCH_CHECK(sources.is_cuda() && sources.dtype() == at::kInt
+              && sources.dim() == 1 && sources.is_contiguous(),
+              who, ": sources must be int32 on device");
+  TORCH_CHECK(col.device() == row_ptr.device()
+              && sources.device() == row_ptr.device(),
+              who, ": tensors on different devices");
+  TORCH_CHECK(row_ptr.numel() >= 1, who, ": row_ptr needs n_nodes + 1 entries");
+  TORCH_CHECK(row_ptr.numel() - 1 <= INT32_MAX,
+              who, ": more nodes than int32 node ids");
+  TORCH_CHECK(col.numel() <= INT32_MAX,
+              who, ": edge count does not fit the int32 row_ptr");
+  TORCH_CHECK(sources.numel() <= INT32_MAX, who, ": too many sources");
+  TORCH_CHECK(levels_per_sync >= 1 && levels_per_sync <= 1024,
+              who, ": levels_per_sync must be in [1, 1024]");
+  TORCH_CHECK(hub_degree >= 1, who, ": hub_degree must be >= 1");
+  TORCH_CHECK(max_hops >= -1, who, ": max_hops must be >= 0, or -1 for none");
+  const int64_t n_nodes = row_ptr.numel() - 1;
+  // value ranges: [rp first, rp last, min rp step, col min, col max,
+  //                src min, src max], neutral values for empty tensors
+  auto l64 = row_ptr.options().dtype(at::kLong);
+  auto scalar = [&](int64_t x) { return at::full({}, x, l64); };
+  std::vector<at::Tensor> probe = {
+      row_ptr[0].to(at::kLong), row_ptr[n_nodes].to(at::kLong),
+      n_nodes ? at::diff(row_ptr).min().to(at::kLong) : scalar(0),
+      col.numel() ? col.min().to(at::kLong) : scalar(0),
+      col.numel() ? col.max().to(at::kLong) : scalar(-1),
+      sources.numel() ? sources.min().to(at::kLong) : scalar(0),
+      sources.numel() ? sources.max().to(at::kLong) : scalar(-1)};
+  auto host = at::stack(probe).cpu();
+  const int64_t* h = host.data_ptr<int64_t>();
+  TORCH_CHECK(h[0] == 0 && h[1] == col.numel() && h[2] >= 0,
+              who, ": row_ptr must rise from 0 to the edge count");
+  TORCH_CHECK(h[3] >= 0 && h[4] < n_nodes, who, ": col value outside [0, n_nodes)");
+  TORCH_CHECK(h[5] >= 0 && h[6] < n_nodes,
+              who, ": source outside [0, n_nodes)");
+}
+
+// -> (source position int32[R], node int32[R], per-source reach counts
+//     int64[S], per-source "reached itself" uint8[S], levels expanded).
+// count_only leaves the two pair columns empty and never allocates them.
+py::tuple path_reach(at::Tensor row_ptr, at::Tensor col, at::Tensor sources,
+                     int64_t max_hops, int64_t levels_per_sync,
+                     int64_t hub_degree, bool count_only) {
+  path_reach_check(row_ptr, col, sources, max_hops, levels_per_sync,
+                   hub_degree);
+  const int64_t n_nodes = row_ptr.numel() - 1;
+  const int64_t S = sources.numel();
+  auto i32 = row_ptr.options();
+  auto i64 = row_ptr.options().dtype(at::kLong);
+  auto counts = at::zeros({S}, i64);
+  auto self_hit = at::zeros({S}, row_ptr.options().dtype(at::kByte));
+  std::vector<at::Tensor> pos_parts, node_parts;
+  int64_t levels = 0;
+  const int hub = static_cast<int>(std::min<int64_t>(hub_degree, INT32_MAX));
+  if (S > 0 && n_nodes > 0 && max_hops != 0) {
+    auto stream = cur_stream();
+    // one allocation so one memset clears all three masks per pass
+    auto masks = at::empty({3, n_nodes}, i64);
+    auto queues = at::empty({2, std::max<int64_t>(n_nodes, kReachBatch)}, i32);
+    auto state = at::empty({kReachStateWords}, i32);
+    auto per_source = at::empty({kReachBatch}, i64);
+    auto node_count = count_only ? at::Tensor() : at::empty({n_nodes}, i32);
+    auto* mbase = reinterpret_cast<unsigned long long*>(
+        masks.data_ptr<int64_t>());
+    unsigned long long* seen = mbase;
+    int32_t* qbase = queues.data_ptr<int32_t>();
+    const int64_t qstride = queues.size(1);
+    uint32_t* st = reinterpret_cast<uint32_t*>(state.data_ptr<int32_t>());
+    const int32_t n32 = static_cast<int32_t>(n_nodes);
+    // one fixed grid for the level and count kernels of every pass
+    const int count_grid = static_cast<int>(std::min<int64_t>(
+        kReachGrid, (n_nodes + kReachBlock - 1) / kReachBlock));
+    bool drained = false;
+    for (int64_t p0 = 0; p0 < S; p0 += kReachBatch) {
+      const int n_src = static_cast<int>(std::min<int64_t>(kReachBatch, S - p0));
+      const int32_t* src = sources.data_ptr<int32_t>() + p0;
+      // a BFS that ran until its queue was empty leaves both frontier
+      // masks zero: only `seen` (first in the allocation) needs clearing
+      HIP_OK(hipMemsetAsync(mbase, 0,
+                            sizeof(int64_t) * (drained ? 1 : 3) * n_nodes,
+                            stream));
+      drained = false;
+      HIP_OK(hipMemsetAsync(st, 0, sizeof(int32_t) * kReachStateWords, stream));
+      HIP_OK(hipMemsetAsync(per_source.data_ptr<int64_t>(), 0,
+                            sizeof(int64_t) * kReachBatch, stream));
+      unsigned long long* cur = mbase + n_nodes;
+      unsigned long long* nxt = mbase + 2 * n_nodes;
+      int32_t* q_in = qbase;
+      int32_t* q_out = qbase + qstride;
+      hipLaunchKernelGGL(path_reach_seed, dim3(1), dim3(kReachBatch), 0,
+                         stream, src, n_src, n32, cur, q_in, st);
+      HIP_OK(hipGetLastError());
+      int slot = 0;
+      int64_t done = 0;
+      int32_t pass_levels = 0;
+      while (max_hops < 0 || done < max_hops) {
+        int64_t group = levels_per_sync;
+        if (max_hops >= 0) group = std::min(group, max_hops - done);
+        for (int64_t g = 0; g < group; ++g) {
+          hipLaunchKernelGGL(path_reach_level, dim3(count_grid),
+                             dim3(kReachBlock), 0, stream,
+                             row_ptr.data_ptr<int32_t>(),
+                             col.data_ptr<int32_t>(), n32, seen, cur, nxt,
+                             q_in, q_out, st, slot, hub);
+          HIP_OK(hipGetLastError());
+          slot = (slot + 1) % 3;
+          std::swap(cur, nxt);
+          std::swap(q_in, q_out);
+        }
+        done += group;
+        auto h = state.cpu();                    // the one sync per group
+        const int32_t* hs = h.data_ptr<int32_t>();
+        TORCH_CHECK(hs[4] == 0, "path_reach: work queue overflow");
+        pass_levels = hs[3];
+        drained = hs[slot] == 0;
+        if (drained) break;
+      }
+      hipLaunchKernelGGL(path_reach_count, dim3(count_grid),
+                         dim3(kReachBlock), 0, stream, seen, n32,
+                         count_only ? nullptr : node_count.data_ptr<int32_t>(),
+                         reinterpret_cast<unsigned long long*>(
+                             per_source.data_ptr<int64_t>()));
+      HIP_OK(hipGetLastError());
+      hipLaunchKernelGGL(path_reach_self, dim3(1), dim3(kReachBatch), 0,
+                         stream, src, n_src, n32, seen,
+                         self_hit.data_ptr<uint8_t>() + p0);
+      HIP_OK(hipGetLastError());
+      counts.narrow(0, p0, n_src).copy_(per_source.narrow(0, 0, n_src));
+      levels += pass_levels;
+      if (count_only) continue;
+      auto incl = at::cumsum(node_count, 0, at::kLong);
+      const int64_t total = incl[n_nodes - 1].item<int64_t>();
+      auto out_pos = at::empty({total}, i32);
+      auto out_node = at::empty({total}, i32);
+      if (total > 0) {
+        hipLaunchKernelGGL(path_reach_emit, dim3(grid_for(n_nodes)),
+                           dim3(kBlock), 0, stream, seen, n32,
+                           incl.data_ptr<int64_t>(),
+                           static_cast<int32_t>(p0), total,
+                           out_pos.data_ptr<int32_t>(),
+                           out_node.data_ptr<int32_t>());
+        HIP_OK(hipGetLastError());
+      }
+      pos_parts.push_back(out_pos);
+      node_parts.push_back(out_node);
+    }
+  }
+  at::Tensor out_pos, out_node;
+  if (pos_parts.empty()) {
+    out_pos = at::empty({0}, i32);
+    out_node = at::empty({0}, i32);
+  } else if (pos_parts.size() == 1) {
+    out_pos = pos_parts[0];
+    out_node = node_parts[0];
+  } else {
+    out_pos = at::cat(pos_parts);
+    out_node = at::cat(node_parts);
+  }
+  return py::make_tuple(out_pos, out_node, counts, self_hit, levels);
+}
+
 // ------------------------------------------------- host bulk N-Triples parse
 // Native replacement for the reference's crossbeam parse pipeline
 // (sparql_database.rs:636-795): one pass tokenizes lines, interns terms in
@@ -5001,6 +5397,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("term_numeric_class", &term_numeric_class,
         "K11 decimal-literal class per term -> uint8 (0 no, 1 yes, "
         "2 undecided)");
+  m.def("path_reach", &path_reach,
+        "K12 multi-source BFS over a CSR adjacency, 64 sources per pass -> "
+        "(source position, node, per-source counts, self-reach, levels)",
+        py::arg("row_ptr"), py::arg("col"), py::arg("sources"),
+        py::arg("max_hops"), py::arg("levels_per_sync"),
+        py::arg("hub_degree"), py::arg("count_only"));
+  m.def("path_reach_batch", []() { return static_cast<int64_t>(kReachBatch); },
+        "sources per path_reach pass");
   m.def("vocab_pack_bytes", &vocab_pack_bytes,
         "annex terms packed as (uint8 blob, int64 lengths)");
 }

@@ -154,7 +154,8 @@ class DistributedDatabase:
             raise ValueError("DistributedDatabase.query supports SELECT/ASK")
         stats = self.global_stats()
         logical = build_logical_plan(sel.where, db, prefixes)
-        physical = Streamertail(stats).find_best_plan(logical)
+        physical = Streamertail(
+            stats, bind_closure_scans=False).find_best_plan(logical)
         physical, part = distribute_plan(physical, stats, self.world,
                                          self.replicated_preds)
         annotate_needed(physical, _top_needed(sel))

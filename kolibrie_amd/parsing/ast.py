@@ -73,7 +73,9 @@ class TriplePatternAst:
     s: str
     p: str
     o: str
-    path_mod: Optional[str] = None   # '+' | '*' transitive-closure steps
+    path_mod: Optional[str] = None   # '+' | '*' closure steps, '?' zero-or-one
+    # (p|q|...) under a modifier: every alternative, `p` holds the first
+    path_alts: Optional[List[str]] = None
 
 
 @dataclass

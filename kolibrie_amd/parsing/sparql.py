@@ -64,7 +64,7 @@ _TOK = re.compile(
     | (?P<var>[?$][A-Za-z_][\w]*)
     | (?P<number>[+-]?(\d+\.\d*|\.\d+|\d+)([eE][+-]?\d+)?)
     | (?P<ruleop>:-)
-    | (?P<op><=|>=|!=|&&|\|\||[=<>!+\-*/^|])
+    | (?P<op><=|>=|!=|&&|\|\||[=<>!+\-*/^|?])
     | (?P<punct>[{}()\[\],;.])
     | (?P<bnode>_:[A-Za-z0-9_.-]+)
     | (?P<pname>[A-Za-z_][\w.-]*:[\w.-]*|:[\w.-]+)
@@ -474,32 +474,39 @@ class Parser:
 
     def _parse_path_steps(self):
         """Property-path subset (engine extension): sequences `p1/p2` and
-        inverse steps `^p`, desugared to fresh-variable join chains."""
+        inverse steps `^p`, desugared to fresh-variable join chains.  A
+        step may carry a modifier: `+`, `*` (closure) or `?` (zero or one
+        step).  Yields (inverse, predicate, modifier, alternatives)."""
         steps = []
         while True:
             inv = False
             if self.at("^"):
                 self.next()
                 inv = True
+            alts = None
             if self.at("("):
-                # alternatives (p1|p2|...): desugar to a variable predicate
-                # constrained by VALUES (engine extension)
                 self.next()
                 alts = [self.parse_term()]
                 while self.at("|"):
                     self.next()
                     alts.append(self.parse_term())
                 self.expect(")")
+                pred = alts[0]
+            else:
+                pred = self.parse_term()
+            mod = None
+            if self.at("+") or self.at("*") or self.at("?"):
+                mod = self.next().text
+            if alts is not None and mod is None:
+                # bare alternatives (p1|p2|...): desugar to a variable
+                # predicate constrained by VALUES (engine extension); under
+                # a modifier the pattern carries them instead
                 pred = self._fresh_path_var()
                 if not hasattr(self, "_alt_values"):
                     self._alt_values = []
                 self._alt_values.append((pred[1:], alts))
-            else:
-                pred = self.parse_term()
-            mod = None
-            if self.at("+") or self.at("*"):
-                mod = self.next().text
-            steps.append((inv, pred, mod))
+                alts = None
+            steps.append((inv, pred, mod, alts))
             if self.at("/"):
                 self.next()
                 continue
@@ -522,12 +529,14 @@ class Parser:
             while True:
                 o = self.parse_term()
                 cur = s
-                for j, (inv, pred, mod) in enumerate(steps):
+                for j, (inv, pred, mod, alts) in enumerate(steps):
                     nxt = o if j == len(steps) - 1 else self._fresh_path_var()
                     if inv:
-                        pats.append(TriplePatternAst(nxt, pred, cur, mod))
+                        pats.append(TriplePatternAst(nxt, pred, cur, mod,
+                                                     alts))
                     else:
-                        pats.append(TriplePatternAst(cur, pred, nxt, mod))
+                        pats.append(TriplePatternAst(cur, pred, nxt, mod,
+                                                     alts))
                     cur = nxt
                 if self.at(","):
                     self.next()
@@ -542,7 +551,8 @@ class Parser:
             break
         if self.at("."):
             self.next()
-        if not allow_alts and getattr(self, "_alt_values", None):
+        if not allow_alts and (getattr(self, "_alt_values", None)
+                               or any(p.path_alts for p in pats)):
             self._alt_values = []
             raise self.err("path alternatives (p|q) are only supported in "
                            "WHERE groups")

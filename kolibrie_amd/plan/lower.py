@@ -84,9 +84,14 @@ def build_logical_plan(
             cp = compile_triple_pattern(pat, prefixes, db)
             pat_scope = scope
             if getattr(pat, "path_mod", None):
-                # p+ / p* closure steps scan a materialized closure index
-                # (built lazily by the executor from the device fixpoint)
-                if not isinstance(cp.p, Constant):
+                # p+ / p* / p? steps: the executor reaches from a bound
+                # endpoint (engine/paths.py) or scans a materialized closure
+                # index.  Scope: ("closure", predicate ids, reflexive,
+                # graph id, hop bound); `?` is one hop at most, reflexive
+                preds = [cp.p]
+                for alt in (getattr(pat, "path_alts", None) or [])[1:]:
+                    preds.append(compile_term(alt, prefixes, db))
+                if not all(isinstance(t, Constant) for t in preds):
                     raise ValueError(
                         "property-path closure requires a constant predicate")
                 if scope is not None and scope[0] != "const":
@@ -94,8 +99,11 @@ def build_logical_plan(
                         "property-path closure under GRAPH ?var is "
                         "unsupported")
                 gid = None if scope is None else scope[1] & 0xFFFFFFFF
-                pat_scope = ("closure", cp.p.id & 0xFFFFFFFF,
-                             pat.path_mod == "*", gid)
+                pids = tuple(sorted({t.id & 0xFFFFFFFF for t in preds}))
+                # the closure index files every pair under the first id
+                cp = TriplePattern(cp.s, Constant(_to_i32(pids[0])), cp.o)
+                pat_scope = ("closure", pids, pat.path_mod in ("*", "?"),
+                             gid, 1 if pat.path_mod == "?" else None)
             scan = LScan(cp, pat_scope)
             node = scan if isinstance(node, LUnit) else LJoin(node, scan)
         return node

@@ -51,8 +51,13 @@ def _pattern_vars(p: TriplePattern) -> List[str]:
 
 
 class Streamertail:
-    def __init__(self, stats: DatabaseStats):
+    def __init__(self, stats: DatabaseStats,
+                 bind_closure_scans: bool = True):
         self.stats = stats
+        # property-path closure scans receive the bindings of the patterns
+        # around them (PBindJoin); the distributed planner keeps them as
+        # hash joins
+        self.bind_closure_scans = bind_closure_scans
         self.est = CostEstimator(stats)
         self.memo = {}
 
@@ -91,8 +96,24 @@ class Streamertail:
             group = self._flatten_scan_group(op)
             if group is not None:
                 return self._plan_scan_group(group, bound)
+            mixed = self._plan_closure_group(op, bound) \
+                if self.bind_closure_scans else None
+            if mixed is not None:
+                return mixed
             lp, lr, lc = self._plan(op.left, bound)
             l_vars = self._out_vars(op.left, bound)
+            if (self.bind_closure_scans and isinstance(op.right, LScan)
+                    and op.right.graph is not None
+                    and op.right.graph[0] == "closure"
+                    and any(isinstance(t, Variable)
+                            and t.name in (bound | l_vars)
+                            for t in (op.right.pattern.s,
+                                      op.right.pattern.o))):
+                # a closure step behind any other subtree that may bind one
+                # of its endpoints: hand it the bindings (rows where the
+                # endpoint is unbound take the closure-index path there)
+                rp = PIndexScan(op.right.pattern, op.right.graph)
+                return PBindJoin(lp, rp), lr, lc + 1000.0 + lr
             rp, rr, rc = self._plan(op.right, bound | l_vars)
             est_rows = max(lr, rr)
             return PHashJoin(lp, rp), est_rows, lc + rc + 2.0 * (lr + rr)
@@ -110,7 +131,7 @@ class Streamertail:
             ip, ir, ic = self._plan(op.input, bound | set(op.variables))
             return PValues(list(op.variables), op.rows, ip), ir * max(1, len(op.rows)), ic
         if isinstance(op, LSubquery):
-            inner = Streamertail(self.stats)
+            inner = Streamertail(self.stats, self.bind_closure_scans)
             sub_plan = inner.find_best_plan(op.select.plan)
             op.select.physical = sub_plan  # attach
             ip, ir, ic = self._plan(op.input, bound)
@@ -151,6 +172,74 @@ class Streamertail:
         if any(s.graph != scope0 for s in scans[1:]):
             return None
         return scans
+
+    def _plan_closure_group(self, op: LogicalOp, bound: Set[str]
+                            ) -> Optional[Tuple[PhysicalOp, float, float]]:
+        """A join tree of scans that differ in scope only because some are
+        property-path closure scans.  The plain scans are planned as a
+        group; each closure scan with an endpoint bound by then (a constant,
+        or a variable the plan so far binds, in either syntactic order)
+        becomes the right side of a PBindJoin, so it receives the bindings
+        and the executor reaches from them instead of building the whole
+        closure.  A closure scan with a constant endpoint seeds the chain.
+        Closure scans with no endpoint bound stay hash joins."""
+        scans: List[LScan] = []
+
+        def rec(x) -> bool:
+            if isinstance(x, LScan):
+                scans.append(x)
+                return True
+            if isinstance(x, LJoin):
+                return rec(x.left) and rec(x.right)
+            return False
+
+        def is_closure(s: LScan) -> bool:
+            return s.graph is not None and s.graph[0] == "closure"
+
+        if not rec(op):
+            return None
+        plain = [s for s in scans if not is_closure(s)]
+        paths = [s for s in scans if is_closure(s)]
+        if not plain or not paths:
+            return None
+        if any(s.graph != plain[0].graph for s in plain[1:]):
+            return None
+
+        def ends(s: LScan):
+            return (s.pattern.s, s.pattern.o)
+
+        cur: Optional[PhysicalOp] = None
+        rows, cost = 1.0, 0.0
+        cur_bound = set(bound)
+        seeds = [s for s in paths
+                 if any(isinstance(t, Constant) for t in ends(s))]
+        for s in seeds:
+            scan_op = PIndexScan(s.pattern, s.graph)
+            cur = scan_op if cur is None else PBindJoin(cur, scan_op)
+            cur_bound.update(_pattern_vars(s.pattern))
+            cost += 1000.0
+        rest = [s for s in paths if s not in seeds]
+        pplan, prows, pcost = self._plan_scan_group(plain, cur_bound)
+        cur = pplan if cur is None else PBindJoin(cur, pplan)
+        rows, cost = max(rows, prows), cost + pcost
+        for s in plain:
+            cur_bound.update(_pattern_vars(s.pattern))
+        while rest:
+            ready = [s for s in rest
+                     if any(isinstance(t, Variable) and t.name in cur_bound
+                            for t in ends(s))]
+            if not ready:
+                break
+            s = ready[0]
+            rest.remove(s)
+            cur = PBindJoin(cur, PIndexScan(s.pattern, s.graph))
+            cur_bound.update(_pattern_vars(s.pattern))
+            cost += 1000.0 + rows
+        for s in rest:
+            sp, sr, sc = self._plan(s, set())
+            cur = PHashJoin(cur, sp)
+            rows, cost = max(rows, sr), cost + sc + 2.0 * (rows + sr)
+        return cur, rows, cost
 
     def _greedy_order(self, scans: List[LScan], bound: Set[str]) -> List[LScan]:
         """Cheapest anchored seed, then only join-connected patterns

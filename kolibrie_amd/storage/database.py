@@ -514,6 +514,49 @@ class SparqlDatabase:
         from ..engine.collation import rank_terms
         return rank_terms(self, ids)
 
+    # ----------------------------------------------------------- reachability
+    def reachable(self, sources, predicates, *, inverse: bool = False,
+                  reflexive: bool = False, max_hops: Optional[int] = None,
+                  graph: Optional[str] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Nodes reachable from each of `sources` along one or more edges
+        whose predicate is one of `predicates`: `(source_ids, node_ids)`,
+        two int32 id tensors on the database's device, one row per distinct
+        (source position, node), in no particular order.  What
+        `<x> (p|q)+ ?y` answers, without the query layer.
+
+        `sources` is a list of term strings or an int32 id tensor
+        (quoted-triple ids included); a source given twice has its rows
+        twice, a source no edge touches has none.  `predicates` is a term
+        string, an id, or a list of either.  `inverse` follows edges
+        backwards, `max_hops` bounds the path length, `graph` names a graph
+        other than the default one.  `reflexive` adds (x, x) for every
+        source that is in the predicates' node set, the rule of `p*`.
+
+        Computed by engine/paths.reach (the K12 kernel on a GPU) over an
+        adjacency cached per store version: the cost follows the edges
+        reached, not the size of the predicate's closure."""
+        from ..engine.paths import reach
+
+        def term_id(t) -> int:
+            if isinstance(t, str):
+                t = self.encode_term_star(t)
+            t = int(t) & 0xFFFFFFFF
+            return t - 0x1_0000_0000 if t >= 0x8000_0000 else t
+
+        if isinstance(sources, torch.Tensor):
+            src = sources.to(device=self.device, dtype=torch.int32).flatten()
+        else:
+            src = torch.tensor([term_id(t) for t in sources],
+                               dtype=torch.int32, device=self.device)
+        if isinstance(predicates, (str, int)):
+            predicates = [predicates]
+        pids = [term_id(p) & 0xFFFFFFFF for p in predicates]
+        gid = None if graph is None else term_id(graph) & 0xFFFFFFFF
+        pos, nodes = reach(self, src, pids, inverse=inverse,
+                           reflexive=reflexive, max_hops=max_hops, gid=gid)
+        return src[pos], nodes
+
     # --------------------------------------------------------- quoted columns
     def quoted_columns(self):
         """Device-resident (s,p,o) int32 columns of the quoted-triple store,
