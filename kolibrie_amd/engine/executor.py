@@ -21,7 +21,8 @@ import torch
 from ..plan.physical import (
     PBind, PBindJoin, PExchange, PFilter, PHashJoin, PIndexScan,
     PInMemoryBuffer,
-    PConstStar, PLeftJoin, PMLPredict, PMinus, PNestedLoopJoin, PStarJoin,
+    PConstStar, PExists, PLeftJoin, PMLPredict, PMinus, PNestedLoopJoin,
+    PStarJoin,
     PSubquery, PTableScan, PUnion, PUnit, PValues, PhysicalOp,
 )
 from ..storage.dataset import DEFAULT_GRAPH, GraphIndex
@@ -37,6 +38,36 @@ from . import tracer
 import logging
 
 _log = logging.getLogger("kolibrie_amd.engine")
+
+# EXISTS auto mode: evaluate the inner group once and semi-join (decorrelated)
+# when its estimated rows are at most this factor times the outer rows, else
+# probe it per row.  The factor is the crossover measured on an MI355X
+# (profiles/exists_measurements.md, section 4) with 4M inner rows and the
+# outer rows swept: the single-pattern probe wins at inner / outer = 1
+# (0.52 ms against 0.61 ms) and above, the two tie at 0.67 (0.69 ms each) and
+# the decorrelated mode wins at 0.4 (0.83 ms against 0.96 ms).
+EXISTS_DECORRELATE_FACTOR = 0.65
+
+
+def exists_decorrelate_factor() -> float:
+    """KOLIBRIE_EXISTS_DECORRELATE_FACTOR overrides the default."""
+    import os
+    v = os.environ.get("KOLIBRIE_EXISTS_DECORRELATE_FACTOR")
+    return float(v) if v else EXISTS_DECORRELATE_FACTOR
+
+
+EXISTS_MODES = ("auto", "probe", "decorrelate", "probed")
+
+
+def exists_mode() -> str:
+    """KOLIBRIE_EXISTS_MODE, default `auto`; an unknown value raises rather
+    than run some mode nobody asked for."""
+    import os
+    mode = os.environ.get("KOLIBRIE_EXISTS_MODE") or "auto"
+    if mode not in EXISTS_MODES:
+        raise ValueError(f"KOLIBRIE_EXISTS_MODE={mode!r}: expected one of "
+                         + ", ".join(EXISTS_MODES))
+    return mode
 
 
 @dataclass
@@ -77,7 +108,7 @@ def _subtree_has_exchange(op: PhysicalOp) -> bool:
         return cached
     found = isinstance(op, PExchange)
     if not found:
-        for name in ("input", "left", "right"):
+        for name in ("input", "left", "right", "sub", "sub_free"):
             child = getattr(op, name, None)
             if isinstance(child, PhysicalOp) and _subtree_has_exchange(child):
                 found = True
@@ -160,10 +191,26 @@ class ExecutionEngine:
             return Bindings.concat([l, r], self.device)
         if isinstance(op, PFilter):
             rows = self.execute(op.input, incoming)
+            # hidden EXISTS columns end here, on empty rows too: a UNION or
+            # SELECT * above must never see them
+            marks = getattr(op.condition, "exists_marks", None)
             if rows.is_empty():
-                return rows
+                return rows.drop_cols(marks) if marks else rows
             mask = op.condition.eval_mask(rows, self.db)
-            return _prune(rows.select(mask), needed)
+            out = rows.select(mask)
+            if marks:
+                out = out.drop_cols(marks)
+            return _prune(out, needed)
+        if isinstance(op, PExists):
+            rows = self.execute(op.input, incoming)
+            if rows.is_empty() and not (_subtree_has_exchange(op.sub)
+                                        or _subtree_has_exchange(op.sub_free)):
+                mask = torch.zeros(0, dtype=torch.bool, device=self.device)
+            else:
+                mask = self._exists_mask(op, rows)
+            cols = dict(rows.cols)
+            cols[op.mark] = mask
+            return Bindings(cols, rows.n, self.device, rows.maybe_unbound)
         if isinstance(op, PBind):
             rows = self.execute(op.input, incoming)
             if rows.is_empty():
@@ -222,6 +269,141 @@ class ExecutionEngine:
             from ..ml.predict import execute_ml_predict
             return execute_ml_predict(op.info, rows, self.db)
         raise ValueError(f"cannot execute {type(op).__name__}")
+
+    # ------------------------------------------------- [NOT] EXISTS (K13) ----
+    def _exists_mask(self, op: PExists, rows: Bindings) -> torch.Tensor:
+        """bool[rows.n]: the truth of `[NOT] EXISTS { P }` for each row.
+
+        Row mu passes EXISTS iff the evaluation of P, with mu's bindings
+        visible to P's FILTERs and BINDs, has a solution compatible with mu
+        (equal on every variable both bind; UNBOUND is compatible with
+        anything).  Shared variables are those of mu that P's patterns can
+        bind, correlated ones those P only reads.  One mode per evaluation,
+        each with an exec_stats counter:
+
+          EXISTS_CONST         nothing shared or correlated: P is evaluated
+                               once from the unit row (COUNT pushdown, no
+                               column); every row passes iff it has a solution
+          EXISTS_DECORRELATED  no correlated variable, every shared one
+                               certain in P, no UNBOUND outer cell: P is
+                               evaluated once from the unit row and the rows
+                               semi-joined against it (K13 on a GPU, then
+                               EXISTS_SEMI_NATIVE too; the torch mirror
+                               elsewhere and beyond four shared variables)
+          EXISTS_PROBE_K1      P is one index scan whose bound positions form
+                               a prefix: count-only K1 probe, nothing emitted
+          EXISTS_PROBED        everything else: the distinct (shared,
+                               correlated) rows get a hidden key id and run
+                               through P as incoming rows; the ids that come
+                               back are marked and gathered through the
+                               inverse.  UNBOUND cells on either side follow
+                               the scans' and joins' own UNBOUND rules.
+
+        KOLIBRIE_EXISTS_MODE=auto|probe|decorrelate forces a mode where it
+        is legal; an illegal forced mode falls back to the probed family.
+        `probed` is a fourth value, for measurement: the general probed mode
+        even where the single-pattern probe would do.  Any other value
+        raises.  Distributed plans (world > 1) run the decorrelated mode
+        only."""
+        from ..plan.physical import op_certain_vars
+        n, dev = rows.n, self.device
+        shared = [v for v in rows.variables if v in op.sub_bind_vars]
+        corr = [v for v in rows.variables
+                if v in op.sub_read_vars and v not in op.sub_bind_vars]
+        unit = Bindings.unit(dev)
+
+        def done(hit: torch.Tensor) -> torch.Tensor:
+            return ~hit if op.negated else hit
+
+        if not shared and not corr:
+            exec_stats.bump("EXISTS_CONST")
+            any_solution = self.execute(op.sub_free, unit).n > 0
+            return torch.full((n,), any_solution != op.negated,
+                              dtype=torch.bool, device=dev)
+        if self.ctx.world > 1:
+            # the distributed planner admits this operator only with no
+            # correlated variable and every shared one certain on both sides
+            # (it raises otherwise, on every rank alike), so no rank decides
+            # differently here and all of them enter sub_free's broadcast
+            mode, decor_ok = "decorrelate", True
+        else:
+            decor_ok = (not corr and not rows.maybe_unbound
+                        and set(shared) <= op_certain_vars(op.sub_free))
+            mode = exists_mode()
+            if mode == "auto" and decor_ok:
+                # rows.n stands in for the distinct outer keys: counting
+                # them would cost the sort this choice tries to avoid
+                mode = "decorrelate" if op.est_sub_rows <= \
+                    exists_decorrelate_factor() * max(1, n) else "probe"
+        if mode == "decorrelate" and decor_ok:
+            exec_stats.bump("EXISTS_DECORRELATED")
+            res = self.execute(op.sub_free, unit)
+            if res.n == 0 or n == 0:
+                return torch.full((n,), op.negated, dtype=torch.bool,
+                                  device=dev)
+            from .tensor_utils import semi_join_mask
+            mask, native = semi_join_mask(
+                [rows.col(v) for v in shared], [res.col(v) for v in shared],
+                op.negated)
+            if native:
+                exec_stats.bump("EXISTS_SEMI_NATIVE")
+            return mask
+        if not corr and not rows.maybe_unbound and mode != "probed":
+            hit = self._exists_probe_k1(op.sub, rows, shared)
+            if hit is not None:
+                exec_stats.bump("EXISTS_PROBE_K1")
+                return done(hit)
+        exec_stats.bump("EXISTS_PROBED")
+        if n == 0:
+            return torch.zeros(0, dtype=torch.bool, device=dev)
+        key_vars = shared + corr
+        gid, n_keys = group_index([rows.col(v) for v in key_vars])
+        rep = torch.empty(n_keys, dtype=torch.long, device=dev)
+        rep[gid] = torch.arange(n, dtype=torch.long, device=dev)
+        key_cols = {v: rows.col(v)[rep] for v in key_vars}
+        key_cols[op.key_var] = torch.arange(n_keys, dtype=torch.int32,
+                                            device=dev)
+        keys = Bindings(key_cols, n_keys, dev, rows.maybe_unbound)
+        res = self.execute(op.sub, keys)
+        marked = torch.zeros(n_keys, dtype=torch.bool, device=dev)
+        if res.n:
+            if not res.has(op.key_var):
+                raise ValueError("EXISTS: the inner plan dropped the key id")
+            marked[res.col(op.key_var).long()] = True
+        return done(marked[gid])
+
+    def _exists_probe_k1(self, sub: PhysicalOp, rows: Bindings,
+                         shared: List[str]) -> Optional[torch.Tensor]:
+        """EXISTS whose inner plan is ONE index scan over a plain graph:
+        per-row hit mask from the count-only K1 probe, or None when the
+        shape does not fit (the caller then runs the probed mode)."""
+        if not isinstance(sub, (PIndexScan, PTableScan)) or rows.n == 0:
+            return None
+        scope = sub.graph
+        if scope is None:
+            idx = self.ctx.default_index()
+        elif scope[0] == "const":
+            idx = self.db.store.graph_index(scope[1] & 0xFFFFFFFF)
+        else:
+            return None
+        consts: Dict[int, int] = {}
+        probes: Dict[int, torch.Tensor] = {}
+        seen = set()
+        for i, t in enumerate(sub.pattern.terms()):
+            if isinstance(t, Constant):
+                consts[i] = t.id
+            elif isinstance(t, Variable):
+                if t.name in seen:
+                    return None          # ?x p ?x: needs the emitted rows
+                seen.add(t.name)
+                if t.name in shared:
+                    probes[i] = rows.col(t.name)
+            else:
+                return None              # quoted-triple pattern
+        if not probes:
+            return None
+        from .scan import scan_probe_exists
+        return scan_probe_exists(idx, consts, probes)
 
     def _exec_exchange(self, op: PExchange, rows: Bindings) -> Bindings:
         """Planner-emitted re-partition.

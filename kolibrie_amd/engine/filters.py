@@ -30,7 +30,8 @@ from typing import Dict, List, Optional
 import torch
 
 from ..parsing.ast import (
-    EAnd, EArith, ECmp, EFunc, ELit, ENot, EOr, EVar, Expr,
+    EAnd, EArith, ECmp, EExists, EExistsMark, EFunc, ELit, ENot, EOr, EVar,
+    Expr,
 )
 from ..storage.terms import UNBOUND
 from .bindings import Bindings
@@ -49,6 +50,11 @@ class CompiledExpr:
         # encode literal terms now (dictionary writes happen at compile time,
         # mirroring utils.rs compile_term)
         self._prepare(ast, db)
+        # hidden columns of the [NOT] EXISTS placeholders in this filter
+        # (plan/lower.py); such a filter composes masks below instead of
+        # compiling to K5 bytecode, and its PFilter drops the columns
+        self.exists_marks: List[str] = []
+        _collect_marks(ast, self.exists_marks)
 
     def _prepare(self, e: Expr, db):
         if isinstance(e, EFunc) and e.name in STRING_PREDICATES:
@@ -73,7 +79,7 @@ class CompiledExpr:
 
     # -------------------------------------------------------------- evaluate
     def eval_mask(self, b: Bindings, db) -> torch.Tensor:
-        if b.n > 0 and b.device.type == "cuda":
+        if b.n > 0 and b.device.type == "cuda" and not self.exists_marks:
             from ..ops import native_for
             from ..ops.filter_bytecode import compile_filter
             probe_col = next(iter(b.cols.values())) if b.cols else None
@@ -113,6 +119,13 @@ def _collect_vars(e: Expr, out: List[str]):
             out.append(e.name)
     for c in _children(e):
         _collect_vars(c, out)
+
+
+def _collect_marks(e: Expr, out: List[str]):
+    if isinstance(e, EExistsMark):
+        out.append(e.column)
+    for c in _children(e):
+        _collect_marks(c, out)
 
 
 def _ids_of(e: Expr, b: Bindings) -> Optional[torch.Tensor]:
@@ -233,6 +246,13 @@ def _eval_bool(e: Expr, b: Bindings, db) -> torch.Tensor:
             return _eval_string_pred(e, b, db)
         # other functions are false in FILTER context (ref types.rs:444-455)
         return torch.zeros(b.n, dtype=torch.bool, device=dev)
+    if isinstance(e, EExistsMark):
+        # the PExists operator below this filter computed the truth of the
+        # whole `[NOT] EXISTS { ... }` term into its hidden column
+        return b.col(e.column)
+    if isinstance(e, EExists):
+        raise ValueError("EXISTS is only supported in FILTER expressions of "
+                         "SELECT / ASK / CONSTRUCT / UPDATE groups")
     if isinstance(e, EVar):
         # bare variable: effective boolean value — bound and != "false"
         if not b.has(e.name):

@@ -23,7 +23,7 @@ class QueryEngine:
         from ..plan.lower import build_logical_plan
         from ..plan.optimizer import Streamertail, annotate_needed
         from ..plan.physical import (
-            PBind, PBindJoin, PFilter, PHashJoin, PIndexScan, PMinus,
+            PBind, PBindJoin, PExists, PFilter, PHashJoin, PIndexScan, PMinus,
             PNestedLoopJoin, PStarJoin, PSubquery, PTableScan, PUnion,
             PUnit, PValues,
         )
@@ -65,6 +65,14 @@ class QueryEngine:
                 rec(op.right, indent + 1)
             elif isinstance(op, PFilter):
                 lines.append(f"{pad}Filter")
+                rec(op.input, indent + 1)
+            elif isinstance(op, PExists):
+                # the probed-mode inner plan, indented under the operator
+                corr = "".join(f" ?{v}" for v in op.correlated_vars)
+                lines.append(f"{pad}{'NotExists' if op.negated else 'Exists'}"
+                             + (f" [correlated:{corr}]" if corr else ""))
+                lines.append(f"{pad}  sub:")
+                rec(op.sub, indent + 2)
                 rec(op.input, indent + 1)
             elif hasattr(op, "input"):
                 lines.append(pad + name)

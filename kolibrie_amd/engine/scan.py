@@ -203,6 +203,11 @@ def scan_probe(
             a_const = consts.get(pos[0], 0)
             b_colp = probes[pos[1]].contiguous() if pos[1] in probes else None
             b_const = consts.get(pos[1], 0)
+            if a_col is None and b_colp is None:
+                # both prefix positions are constants and the probe column
+                # is post-filtered (?x <p> <o> probed on ?x): the kernel
+                # wants a per-row column, so the first constant becomes one
+                a_col = col_for(pos[0]).contiguous()
             li, b_col, z_col = native.probe_fused(
                 key12, z, a_col, a_const, b_colp, b_const, [], True)
         else:
@@ -306,6 +311,62 @@ def scan_probe_count(idx: GraphIndex, consts: Dict[int, int],
         lo = torch.searchsorted(key12, pack2(v, torch.zeros_like(v)), side="left")
         hi = torch.searchsorted(key12, pack2(v, torch.full_like(v, -1)), side="right")
     return int((hi - lo).sum().item())
+
+
+def scan_probe_exists(idx: GraphIndex, consts: Dict[int, int],
+                      probes: Dict[int, torch.Tensor]
+                      ) -> Optional[torch.Tensor]:
+    """Per-row existence probe: bool[n_rows], row i has any match.  Emits
+    nothing.
+
+    Returns None where scan_probe_count does (a post-filter position would
+    be required): the caller falls back to the emitting path."""
+    cnt = _probe_row_counts(idx, consts, probes)
+    return None if cnt is None else cnt > 0
+
+
+def _probe_row_counts(idx: GraphIndex, consts: Dict[int, int],
+                      probes: Dict[int, torch.Tensor]
+                      ) -> Optional[torch.Tensor]:
+    """Matches per probe row, with no emit pass: the count-only K1 kernels on
+    a device, the searchsorted pair elsewhere.  None when a post-filter
+    position would be required.  (scan_probe_count computes the sum of the
+    same counts with code of its own.)"""
+    n_rows = next(iter(probes.values())).numel()
+    if idx.n == 0 or n_rows == 0:
+        return torch.zeros(n_rows, dtype=torch.long, device=idx.device)
+    bound = set(consts.keys()) | set(probes.keys())
+    code, plen = choose_order(bound, set(consts.keys()))
+    pos = _ORDER_POS[code]
+    if plen == 0 or (bound - set(pos[:plen])):
+        return None
+    key12, _z = idx.orders[code]
+
+    def col_for(position: int) -> torch.Tensor:
+        if position in probes:
+            return probes[position]
+        return torch.full((n_rows,), consts[position], dtype=torch.int32,
+                          device=idx.device)
+
+    from ..ops import native_for
+    native = native_for(key12)
+    if native is not None:
+        if plen == 2:
+            keys = pack2(col_for(pos[0]).contiguous(),
+                         col_for(pos[1]).contiguous())
+            cnt = native.probe_exact_counts(key12, keys.contiguous())
+        else:
+            cnt = native.probe_range_counts(key12, col_for(pos[0]).contiguous())
+        return cnt
+    if plen == 2:
+        keys = pack2(col_for(pos[0]), col_for(pos[1]))
+        lo = torch.searchsorted(key12, keys, side="left")
+        hi = torch.searchsorted(key12, keys, side="right")
+    else:
+        v = col_for(pos[0])
+        lo = torch.searchsorted(key12, pack2(v, torch.zeros_like(v)), side="left")
+        hi = torch.searchsorted(key12, pack2(v, torch.full_like(v, -1)), side="right")
+    return hi - lo
 
 
 def scan_unit_count(idx: GraphIndex, consts: Dict[int, int]) -> Optional[int]:

@@ -131,6 +131,31 @@ def membership_mask(a_cols: Rows, b_sorted_unique: Rows) -> torch.Tensor:
     return mask[:n_a]
 
 
+def semi_join_mask_torch(probe_cols: Rows, build_cols: Rows,
+                         anti: bool = False) -> torch.Tensor:
+    """bool[l]: probe row i has an equal build row, flipped by `anti`.
+
+    The torch mirror of the K13 semi_join kernel: the CPU execution path of
+    decorrelated EXISTS, the oracle of the GPU tests, and what
+    KOLIBRIE_FORCE_TORCH_FALLBACK=1 selects on a device.  Any number of key
+    columns; no key cell may be UNBOUND (the caller checks)."""
+    hit = membership_mask(list(probe_cols), unique_rows(list(build_cols)))
+    return ~hit if anti else hit
+
+
+def semi_join_mask(probe_cols: Rows, build_cols: Rows,
+                   anti: bool = False) -> Tuple[torch.Tensor, bool]:
+    """(mask, ran natively): K13 on a device for up to four key columns,
+    the torch mirror elsewhere."""
+    from ..ops import native_for
+    native = native_for(probe_cols[0]) if len(probe_cols) <= 4 else None
+    if native is None:
+        return semi_join_mask_torch(probe_cols, build_cols, anti), False
+    out = native.semi_join_mask([c.contiguous() for c in probe_cols],
+                                [c.contiguous() for c in build_cols], anti)
+    return out.view(torch.bool), True
+
+
 def merge_join_indices(
     left_key: torch.Tensor, right_key: torch.Tensor
 ) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -368,6 +368,145 @@ __global__ void hj_emit(KeyCols probe, int64_t l, KeyCols build, int64_t r,
   }
 }
 
+// ------------------------------------------------------------ K13: semi join
+// Does probe row i have ANY build row with an equal key?  One byte per probe
+// row, flipped by `anti` (NOT EXISTS).  No sort, no match counts, no emit.
+//
+// One or two key columns pack into one 64-bit key, and the build side becomes
+// an open-addressing key SET: duplicates of a build key (the normal case, a
+// pattern projected to its subject) collapse into one slot.  The halves are
+// masked, not sign-extended: quoted-triple ids are negative int32.  kSemiEmpty
+// is no real key: a bound two-column key would need both halves -1 (UNBOUND),
+// and a one-column key has a zero low half.
+//
+// Three or four key columns reuse the K2 chained table; hj_exists leaves the
+// chain at the first match.
+constexpr unsigned long long kSemiEmpty = ~0ull;
+constexpr int kSemiLdsSlots = 8192;   // 64 KB of keys: the LDS tier's limit
+constexpr int kSemiMinSlots = 256;    // table floor (a power of two)
+// The LDS tier copies the whole finished table into every block.  Measured
+// (profiles/exists_measurements.md, section 3) it never repaid the copy: with
+// 489 and 4883 probe rows per block and tables of 256, 2048 and 8192 slots it
+// took as long as the table in global memory or up to 1.3x longer, so no
+// amortisation bound selects it; only `lds_tier` = 1 does.
+
+__device__ __forceinline__ unsigned long long semi_key(const KeyCols& kc,
+                                                       int64_t row) {
+  unsigned long long a = static_cast<uint32_t>(kc.c[0][row]);
+  unsigned long long b = kc.k > 1 ? static_cast<uint32_t>(kc.c[1][row]) : 0u;
+  return (a << 32) | b;
+}
+
+__device__ __forceinline__ uint32_t semi_hash(unsigned long long x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ULL;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBULL;
+  return static_cast<uint32_t>(x ^ (x >> 31));
+}
+
+// The table has >= 2r slots, so the load stays <= 0.5 and every walk ends.
+__global__ void semi_set_build(KeyCols build, int64_t r, uint32_t mask,
+                               unsigned long long* __restrict__ table) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < r;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    unsigned long long key = semi_key(build, i);
+    uint32_t h = semi_hash(key) & mask;
+    for (;;) {
+      // a slot only ever goes EMPTY -> key, so a plain load that already
+      // shows the key spares the atomic (duplicate build keys)
+      unsigned long long cur = table[h];
+      if (cur == key) break;
+      if (cur == kSemiEmpty) {
+        // device-scope atomic (cross-XCD safe, guide G12)
+        cur = atomicCAS(&table[h], kSemiEmpty, key);
+        if (cur == kSemiEmpty || cur == key) break;
+      }
+      h = (h + 1) & mask;
+    }
+  }
+}
+
+__device__ __forceinline__ void semi_probe_rows(
+    const KeyCols& probe, int64_t l, const unsigned long long* table,
+    uint32_t mask, uint8_t anti, uint8_t* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < l;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    unsigned long long key = semi_key(probe, i);
+    uint32_t h = semi_hash(key) & mask;
+    uint8_t found = 0;
+    for (;;) {
+      unsigned long long cur = table[h];
+      if (cur == key) { found = 1; break; }
+      if (cur == kSemiEmpty) break;
+      h = (h + 1) & mask;
+    }
+    out[i] = found ^ anti;
+  }
+}
+
+// kLds: the finished table (mask + 1 <= kSemiLdsSlots slots) is copied into
+// LDS with 16-byte loads, a plain copy and not a rebuild, then probed there.
+template <bool kLds>
+__global__ void semi_set_probe(KeyCols probe, int64_t l,
+                               const unsigned long long* __restrict__ table,
+                               uint32_t mask, uint8_t anti,
+                               uint8_t* __restrict__ out) {
+  if constexpr (kLds) {
+    __shared__ __attribute__((aligned(16)))
+        unsigned long long lds_table[kSemiLdsSlots];
+    const uint4* src = reinterpret_cast<const uint4*>(table);
+    uint4* dst = reinterpret_cast<uint4*>(lds_table);
+    const int n16 = static_cast<int>((mask + 1u) >> 1);   // two slots a load
+    for (int j = threadIdx.x; j < n16; j += blockDim.x) dst[j] = src[j];
+    __syncthreads();
+    semi_probe_rows(probe, l, lds_table, mask, anti, out);
+  } else {
+    semi_probe_rows(probe, l, table, mask, anti, out);
+  }
+}
+
+__device__ __forceinline__ void hj_exists_rows(
+    const KeyCols& probe, int64_t l, const KeyCols& build,
+    const int32_t* heads, const int32_t* next, uint32_t mask, uint8_t anti,
+    uint8_t* __restrict__ out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < l;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & mask;
+    uint8_t found = 0;
+    for (int32_t b = heads[h]; b >= 0; b = next[b])
+      if (keys_equal(probe, i, build, b)) { found = 1; break; }
+    out[i] = found ^ anti;
+  }
+}
+
+// hj_count without the count: the chain walk leaves at the first match.
+template <bool kLds>
+__global__ void hj_exists(KeyCols probe, int64_t l, KeyCols build, int64_t r,
+                          const int32_t* __restrict__ heads,
+                          const int32_t* __restrict__ next, uint32_t mask,
+                          uint8_t anti, uint8_t* __restrict__ out) {
+  if constexpr (kLds) {
+    __shared__ int32_t lds_heads[kHjLdsSlots];
+    __shared__ int32_t lds_next[kHjLdsRows];
+    // the staging of hj_lds_build, on the kernel argument itself: a copy of
+    // KeyCols indexed in a loop would live in scratch
+    for (int j = threadIdx.x; j < kHjLdsSlots; j += blockDim.x)
+      lds_heads[j] = -1;
+    __syncthreads();
+    for (int64_t i = threadIdx.x; i < r; i += blockDim.x) {
+      uint32_t h =
+          static_cast<uint32_t>(mix_hash(build, i)) & (kHjLdsSlots - 1);
+      lds_next[i] = atomicExch(&lds_heads[h], static_cast<int32_t>(i));
+    }
+    __syncthreads();
+    hj_exists_rows(probe, l, build, lds_heads, lds_next, kHjLdsSlots - 1, anti,
+                   out);
+  } else {
+    hj_exists_rows(probe, l, build, heads, next, mask, anti, out);
+  }
+}
+
 // ------------------------------------------------------------ K5: filter VM
 // Postfix bytecode over binding columns.  Opcodes (engine/filter_bytecode.py
 // must match):
@@ -3105,6 +3244,62 @@ std::vector<at::Tensor> hash_join(std::vector<at::Tensor> left_cols,
   return {li, ri};
 }
 
+// K13 semi join: out[i] = (probe row i has an equal build row) ^ anti.
+// The caller guarantees that no key cell is UNBOUND.  lds_tier: 1 takes the
+// key set's LDS tier where the table fits it, anything else the table in
+// global memory (the tier lost every measurement, see kSemiLdsSlots; the
+// chained table of 3-4 columns ignores the knob).
+at::Tensor semi_join_mask(std::vector<at::Tensor> probe_cols,
+                          std::vector<at::Tensor> build_cols, bool anti,
+                          int64_t lds_tier) {
+  HjSides s = hj_sides(probe_cols, build_cols);
+  for (size_t j = 0; j < probe_cols.size(); ++j) {
+    TORCH_CHECK(probe_cols[j].dim() == 1 && build_cols[j].dim() == 1 &&
+                    probe_cols[j].is_contiguous() &&
+                    build_cols[j].is_contiguous(),
+                "semi_join_mask: key columns must be contiguous 1-D");
+    TORCH_CHECK(probe_cols[j].numel() == s.l && build_cols[j].numel() == s.r,
+                "semi_join_mask: key columns of one side differ in length");
+    TORCH_CHECK(probe_cols[j].device() == probe_cols[0].device() &&
+                    build_cols[j].device() == probe_cols[0].device(),
+                "semi_join_mask: key columns on different devices");
+  }
+  auto opts_int = probe_cols[0].options();
+  auto opts_u8 = opts_int.dtype(at::kByte);
+  const uint8_t flip = anti ? 1 : 0;
+  if (s.l == 0) return at::empty({0}, opts_u8);
+  if (s.r == 0) return at::full({s.l}, static_cast<int64_t>(flip), opts_u8);
+  auto stream = cur_stream();
+  auto out = at::empty({s.l}, opts_u8);
+  if (s.probe.k > 2) {
+    HjTable t = hj_table(s, opts_int, stream);
+    hipLaunchKernelGGL(t.lds ? hj_exists<true> : hj_exists<false>,
+                       dim3(grid_for(s.l)), dim3(kBlock), 0, stream, s.probe,
+                       s.l, s.build, s.r, t.heads.data_ptr<int32_t>(),
+                       t.next.data_ptr<int32_t>(), t.mask, flip,
+                       out.data_ptr<uint8_t>());
+    HIP_OK(hipGetLastError());
+    return out;
+  }
+  // key set: next power of two >= 2r slots, all EMPTY (-1 is ~0ull)
+  int64_t slots = kSemiMinSlots;
+  while (slots < 2 * s.r) slots <<= 1;
+  TORCH_CHECK(slots <= (int64_t{1} << 32), "semi_join_mask: build side too large");
+  const uint32_t mask = static_cast<uint32_t>(slots - 1);
+  auto table = at::full({slots}, -1, opts_int.dtype(at::kLong));
+  auto* tab = reinterpret_cast<unsigned long long*>(table.data_ptr<int64_t>());
+  hipLaunchKernelGGL(semi_set_build, dim3(grid_for(s.r)), dim3(kBlock), 0,
+                     stream, s.build, s.r, mask, tab);
+  HIP_OK(hipGetLastError());
+  const bool lds = lds_tier > 0 && slots <= kSemiLdsSlots;
+  hipLaunchKernelGGL(lds ? semi_set_probe<true> : semi_set_probe<false>,
+                     dim3(grid_for(s.l)), dim3(kBlock), 0, stream, s.probe,
+                     s.l, tab,
+                     mask, flip, out.data_ptr<uint8_t>());
+  HIP_OK(hipGetLastError());
+  return out;
+}
+
 // K5 filter bytecode evaluation -> bool mask.
 at::Tensor filter_bytecode(at::Tensor ops, at::Tensor args, at::Tensor consts,
                            std::vector<at::Tensor> cols, at::Tensor value_col,
@@ -5377,6 +5572,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K1 count-only range probe -> per-row match counts");
   m.def("hash_join_counts", &hash_join_counts,
         "K2 count-only hash join -> per-left-row match counts");
+  m.def("semi_join_mask", &semi_join_mask, py::arg("probe_cols"),
+        py::arg("build_cols"), py::arg("anti"), py::arg("lds_tier") = -1,
+        "K13 semi join -> uint8 per probe row: has an equal build row, "
+        "flipped by anti");
   m.def("filter_bytecode", &filter_bytecode,
         "K5 filter bytecode evaluation -> bool mask");
   m.def("str_match", &str_match,

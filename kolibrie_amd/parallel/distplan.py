@@ -33,7 +33,8 @@ from dataclasses import dataclass
 from typing import Optional, Set, Tuple, Union
 
 from ..plan.physical import (
-    PBind, PBindJoin, PConstStar, PExchange, PFilter, PHashJoin, PIndexScan,
+    PBind, PBindJoin, PConstStar, PExchange, PExists, PFilter, PHashJoin,
+    PIndexScan,
     PInMemoryBuffer, PLeftJoin, PMLPredict, PMinus, PNestedLoopJoin,
     PProjection, PStarJoin, PSubquery, PTableScan, PUnion, PUnit, PValues,
     PhysicalOp, op_certain_vars,
@@ -103,6 +104,8 @@ class DistPlanner:
             return max(self._est_rows(op.left), self._est_rows(op.right))
         if isinstance(op, (PMinus, PLeftJoin)):
             return self._est_rows(op.left)
+        if isinstance(op, PExists):
+            return self._est_rows(op.input)
         if isinstance(op, PInMemoryBuffer) and op.bindings is not None:
             return float(op.bindings.n)
         return float("inf")  # unknown (subquery/ML): never auto-broadcast
@@ -208,6 +211,36 @@ class DistPlanner:
                 r, rp = self._bcast(r, rp)
             op.left, op.right = l, r
             return op, lp
+        if isinstance(op, PExists):
+            # only the decorrelated mode runs distributed: the inner group is
+            # evaluated once from the unit row (`sub_free`) and every rank
+            # semi-joins its own rows against it, so the rows must see the
+            # GLOBAL inner solutions unless both sides are co-partitioned on
+            # a certain shared key.  The probed plan (`sub`) stays unused.
+            if op.correlated_vars:
+                raise ValueError(
+                    "correlated EXISTS (the inner group reads "
+                    + ", ".join("?" + v for v in op.correlated_vars)
+                    + " from outside) is not supported in distributed plans")
+            # decided here, from the plan alone, so that every rank raises
+            # together: a rank that raised at run time on its own rows would
+            # leave the others waiting in the broadcast below
+            shared = phys_out_vars(op.input) & set(op.sub_bind_vars)
+            loose = shared - (op_certain_vars(op.input)
+                              & op_certain_vars(op.sub_free))
+            if loose:
+                raise ValueError(
+                    "EXISTS whose rows or inner group may leave the shared "
+                    + ", ".join("?" + v for v in sorted(loose))
+                    + " UNBOUND is not supported in distributed plans")
+            child, part = self.distribute(op.input)
+            inner, ipart = self.distribute(op.sub_free)
+            key = self._pick_key(op.input, op.sub_free, shared, part, ipart)
+            if not (key is not None and part == ("hash", key)
+                    and ipart == ("hash", key)):
+                inner, ipart = self._bcast(inner, ipart)
+            op.input, op.sub_free = child, inner
+            return op, part
         if isinstance(op, (PHashJoin, PNestedLoopJoin)):
             return self._dist_join(op)
         if isinstance(op, PBindJoin):

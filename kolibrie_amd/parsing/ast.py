@@ -67,6 +67,29 @@ class EFunc(Expr):
     args: List[Expr]
 
 
+@dataclass
+class EExists(Expr):
+    """`[NOT] EXISTS { group }` inside a FILTER expression.
+
+    A row mu of the enclosing group passes `EXISTS { P }` iff the inner
+    evaluation of P has a solution compatible with mu (equal on every
+    variable both bind; an UNBOUND cell on either side is compatible with
+    anything).  The inner evaluation sees mu's bindings, so FILTERs and
+    BINDs inside P may read variables bound only outside P.  With no shared
+    and no correlated variable every row passes iff P has any solution --
+    which is where NOT EXISTS and MINUS differ.  Variables bound only
+    inside P are local and never reach the output."""
+    group: "GGP"
+    negated: bool = False
+
+
+@dataclass
+class EExistsMark(Expr):
+    """Placeholder the lowering leaves where an EExists stood: reads the
+    hidden boolean column that the PExists operator appended."""
+    column: str
+
+
 # --------------------------------------------------------------- patterns ---
 @dataclass
 class TriplePatternAst:

@@ -16,7 +16,8 @@ import re
 from typing import Dict, List, Optional
 
 from .ast import (
-    CombinedQuery, CombinedRule, EAnd, EArith, ECmp, EFunc, ELit, ENot, EOr,
+    CombinedQuery, CombinedRule, EAnd, EArith, ECmp, EExists, EFunc, ELit,
+    ENot, EOr,
     EVar, Expr, GBgp, GBind, GFilter, GGP, GGraph, GJoin, GMinus, GOptional,
     GSubQuery,
     GUnion, GUnit, GValues, GWindowBlock, ModelDecl, NeuralRelationDecl,
@@ -123,6 +124,9 @@ class Parser:
         self.text = text
         self.toks = _tokenize(text)
         self.i = 0
+        # where [NOT] EXISTS may not stand: the name of the enclosing
+        # construct (BIND, HAVING, a rule body, ...) or None
+        self._exists_forbidden: Optional[str] = None
 
     # ------------------------------------------------------------- helpers --
     def peek(self, ahead: int = 0) -> Optional[_Tok]:
@@ -162,6 +166,31 @@ class Parser:
     def err(self, msg: str) -> ParseError:
         t = self.peek()
         return ParseError(msg, self.text, t.pos if t else len(self.text))
+
+    def _at_exists(self, ahead: int = 0) -> bool:
+        """At `EXISTS {` or `NOT EXISTS {`, `ahead` tokens on."""
+        if self.at_kw("NOT", ahead=ahead):
+            ahead += 1
+        return self.at_kw("EXISTS", ahead=ahead) and self.at("{", ahead + 1)
+
+    def _reject_exists_here(self, where: str):
+        """Raise at a `[FILTER] [NOT] EXISTS {` that stands where the
+        grammar has no expression or group to hold it."""
+        if self._at_exists() or (self.at_kw("FILTER") and (
+                self._at_exists(1)
+                or (self.at("(", 1) and self._at_exists(2)))):
+            raise self.err(f"EXISTS is not supported in {where}")
+
+    def _forbidding_exists(self, where: Optional[str], parse):
+        """Run `parse()` with EXISTS rejected (where names the construct);
+        an enclosing prohibition stays in force."""
+        saved = self._exists_forbidden
+        if where is not None:
+            self._exists_forbidden = where
+        try:
+            return parse()
+        finally:
+            self._exists_forbidden = saved
 
     # ---------------------------------------------------------------- terms --
     def parse_term(self) -> str:
@@ -331,14 +360,17 @@ class Parser:
                     q.group_by.append(self.next().text[1:])
             elif self.at_kw("HAVING"):
                 self.next()
-                q.having = self.parse_filter_expr()
+                q.having = self._forbidding_exists(
+                    "HAVING", self.parse_filter_expr)
             elif self.at_kw("ORDER"):
                 self.next()
                 self.expect_kw("BY")
                 while True:
+                    self._reject_exists_here("ORDER BY")
                     if self.at_kw("ASC") or self.at_kw("DESC"):
                         d = self.next().upper() == "DESC"
                         self.expect("(")
+                        self._reject_exists_here("ORDER BY")
                         v = self.next()
                         self.expect(")")
                         q.order_by.append(OrderCondition(v.text[1:], d))
@@ -409,7 +441,8 @@ class Parser:
             elif self.at_kw("WINDOW"):
                 self.next()
                 w = self.parse_term()
-                inner = self.parse_group()
+                inner = self._forbidding_exists("an RSP WINDOW block",
+                                                self.parse_group)
                 current = self._join(current, GWindowBlock(w, inner))
             elif self.at_kw("FILTER"):
                 self.next()
@@ -417,7 +450,7 @@ class Parser:
             elif self.at_kw("BIND"):
                 self.next()
                 self.expect("(")
-                expr = self.parse_expr()
+                expr = self._forbidding_exists("BIND", self.parse_expr)
                 self.expect_kw("AS")
                 v = self.next()
                 if v.kind != "var":
@@ -648,6 +681,17 @@ class Parser:
         if self.at("!"):
             self.next()
             return ENot(self.parse_unary())
+        if self._at_exists():
+            # [NOT] EXISTS { group }: the group's own FILTERs may hold
+            # further EXISTS (the recursion nests them)
+            if self._exists_forbidden is not None:
+                raise self.err(
+                    f"EXISTS is not supported in {self._exists_forbidden}")
+            negated = self.at_kw("NOT")
+            if negated:
+                self.next()
+            self.next()
+            return EExists(self.parse_group(), negated)
         if self.at("("):
             self.next()
             e = self.parse_expr()
@@ -837,7 +881,8 @@ class Parser:
             windows.append(self.parse_from_named_window())
         if self.at_kw("WHERE"):
             self.next()
-            sel.where = self.parse_group()
+            sel.where = self._forbidding_exists("an RSP query",
+                                                self.parse_group)
         # trailing modifiers
         while True:
             if self.at_kw("GROUP"):
@@ -847,7 +892,8 @@ class Parser:
                     sel.group_by.append(self.next().text[1:])
             elif self.at_kw("HAVING"):
                 self.next()
-                sel.having = self.parse_filter_expr()
+                sel.having = self._forbidding_exists(
+                    "HAVING", self.parse_filter_expr)
             elif self.at_kw("LIMIT"):
                 self.next()
                 sel.limit = int(self.next().text)
@@ -989,7 +1035,7 @@ class Parser:
             conclusions.extend(self.parse_triples_block().patterns)
         self.expect("}")
         self.expect_kw("WHERE")
-        body = self.parse_group()
+        body = self._forbidding_exists("a rule body", self.parse_group)
         if self.at("."):
             self.next()
         ml_predict = None
@@ -1122,6 +1168,7 @@ class Parser:
                     if self.at("."):
                         self.next()
                         continue
+                    self._reject_exists_here("neural-relation inputs")
                     out["input"].extend(self.parse_triples_block().patterns)
                 self.expect("}")
             elif self.peek().kind == "var":
@@ -1198,6 +1245,7 @@ class Parser:
                     if self.at("."):
                         self.next()
                         continue
+                    self._reject_exists_here("neural-relation inputs")
                     pats.extend(self.parse_triples_block().patterns)
                 self.expect("}")
                 decl.options["input_patterns"] = repr(

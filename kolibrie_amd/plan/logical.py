@@ -96,6 +96,16 @@ class LLeftJoin(LogicalOp):
     right: LogicalOp = field(default_factory=LUnit)
 
 
+@dataclass
+class LExists(LogicalOp):
+    """One `[NOT] EXISTS { group }` pulled out of a FILTER expression: marks
+    each input row in the hidden column `mark` (semantics: ast.EExists)."""
+    sub: LogicalOp = field(default_factory=LUnit)   # the inner group
+    mark: str = ""
+    negated: bool = False
+    input: LogicalOp = field(default_factory=LUnit)
+
+
 def scans_of(op: LogicalOp) -> List[LScan]:
     out: List[LScan] = []
 

@@ -6,18 +6,21 @@ time), so execution is pure-int32.
 """
 from __future__ import annotations
 
+import dataclasses
+import itertools
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
 from ..engine.filters import CompiledBind, CompiledExpr
 from ..parsing.ast import (
+    EAnd, EArith, ECmp, EExists, EExistsMark, EFunc, ENot, EOr, Expr,
     GBgp, GBind, GFilter, GGP, GGraph, GJoin, GMinus, GOptional, GSubQuery,
     GUnion,
     GUnit, GValues, GWindowBlock, SelectQuery, TriplePatternAst,
 )
 from ..storage.terms import Constant, QuotedTriplePattern, TriplePattern, Variable
 from .logical import (
-    GraphScope, LBind, LJoin, LScan, LSelection,
+    GraphScope, LBind, LExists, LJoin, LScan, LSelection,
     LSubquery, LUnion, LUnit, LValues, LogicalOp,
 )
 
@@ -73,6 +76,35 @@ class CompiledSubquery:
     physical: object = None  # filled by the optimizer
 
 
+_exists_marks = itertools.count()
+
+
+def _extract_exists(e: Expr, found: list) -> Expr:
+    """Copy of `e` with every EExists replaced by an EExistsMark; appends
+    (mark column, EExists) to `found`.  The column name starts with NUL, so
+    it can never clash with a user variable.  The parsed AST stays as it
+    is: only the path down to a replaced node is copied."""
+    if isinstance(e, EExists):
+        mark = f"\x00exists{next(_exists_marks)}"
+        found.append((mark, e))
+        return EExistsMark(mark)
+    if isinstance(e, (EAnd, EOr, ECmp, EArith)):
+        left = _extract_exists(e.left, found)
+        right = _extract_exists(e.right, found)
+        if left is e.left and right is e.right:
+            return e
+        return dataclasses.replace(e, left=left, right=right)
+    if isinstance(e, ENot):
+        inner = _extract_exists(e.inner, found)
+        return e if inner is e.inner else ENot(inner)
+    if isinstance(e, EFunc):
+        args = [_extract_exists(a, found) for a in e.args]
+        if all(a is b for a, b in zip(args, e.args)):
+            return e
+        return EFunc(e.name, args)
+    return e
+
+
 def build_logical_plan(
     g: GGP, db, prefixes: Dict[str, str], scope: GraphScope = None
 ) -> LogicalOp:
@@ -121,10 +153,18 @@ def build_logical_plan(
         inner_scope = compile_graph_term(g.graph, prefixes, db)
         return build_logical_plan(g.inner, db, prefixes, inner_scope)
     if isinstance(g, GFilter):
-        return LSelection(
-            CompiledExpr(g.expr, db, prefixes),
-            build_logical_plan(g.inner, db, prefixes, scope),
-        )
+        # every [NOT] EXISTS leaves the expression for an operator of its
+        # own below the selection; the expression keeps a placeholder that
+        # reads the operator's hidden column.  The inner group lowers in the
+        # same graph scope.
+        found: list = []
+        expr = _extract_exists(g.expr, found)
+        node = build_logical_plan(g.inner, db, prefixes, scope)
+        for mark, ex in found:
+            node = LExists(
+                build_logical_plan(ex.group, db, prefixes, scope),
+                mark, ex.negated, node)
+        return LSelection(CompiledExpr(expr, db, prefixes), node)
     if isinstance(g, GBind):
         return LBind(
             CompiledBind(g.expr, db, prefixes),

@@ -23,13 +23,13 @@ from typing import List, Optional, Set, Tuple
 from ..storage.terms import Constant, TriplePattern, Variable
 from .cost import CostEstimator
 from .logical import (
-    LBind, LJoin, LLeftJoin, LMLPredict, LMinus, LProjection, LScan,
+    LBind, LExists, LJoin, LLeftJoin, LMLPredict, LMinus, LProjection, LScan,
     LSelection,
     LSubquery, LUnion, LUnit, LValues, LogicalOp,
 )
 from .physical import (
     PBind, PBindJoin, PConstStar, PFilter, PHashJoin, PIndexScan,
-    PLeftJoin, PMLPredict, PMinus,
+    PExists, PLeftJoin, PMLPredict, PMinus,
     PNestedLoopJoin, PProjection, PStarJoin, PSubquery, PTableScan, PUnion,
     PUnit, PValues, PhysicalOp,
 )
@@ -136,6 +136,23 @@ class Streamertail:
             op.select.physical = sub_plan  # attach
             ip, ir, ic = self._plan(op.input, bound)
             return PSubquery(op.select, ip), ir, ic
+        if isinstance(op, LExists):
+            # the inner group gets optimizers of its own, as LSubquery does:
+            # `sub` is planned with the outer variables bound (a closure
+            # step or scan inside may then be bind-joined to the rows it
+            # receives), `sub_free` for one evaluation from the unit row
+            ip, ir, ic = self._plan(op.input, bound)
+            outer = set(bound) | _logical_out_vars(op.input)
+            sp, _sr, sc = Streamertail(
+                self.stats, self.bind_closure_scans)._plan(op.sub, outer)
+            fp, fr, _fc = Streamertail(
+                self.stats, self.bind_closure_scans)._plan(op.sub, set())
+            binds = _logical_out_vars(op.sub)
+            reads = _logical_mentioned_vars(op.sub)
+            correlated = tuple(sorted((outer & reads) - binds))
+            return (PExists(ip, sp, fp, op.mark, op.negated, correlated,
+                            frozenset(binds), frozenset(reads), fr),
+                    max(1.0, ir / 2.0), ic + sc + ir)
         if isinstance(op, LMLPredict):
             ip, ir, ic = self._plan(op.input, bound)
             return PMLPredict(op.info, ip), ir, ic + 1000.0 + 100.0 * ir
@@ -481,6 +498,34 @@ def _logical_out_vars(op: LogicalOp) -> Set[str]:
         return out
 
 
+def _logical_mentioned_vars(op: LogicalOp) -> Set[str]:
+    """Every variable a logical subtree binds OR reads: patterns, VALUES,
+    FILTER and BIND expressions, sub-selects and nested EXISTS groups.  The
+    part of it that the rows outside an EXISTS bind is what the inner
+    evaluation has to see."""
+    out: Set[str] = set(_logical_out_vars(op))
+
+    def rec(x):
+        if isinstance(x, LSelection):
+            out.update(x.condition.variables())
+        elif isinstance(x, LBind):
+            from ..engine.filters import _collect_vars
+            vs: List[str] = []
+            _collect_vars(x.expr.ast, vs)
+            out.update(vs)
+        elif isinstance(x, LSubquery):
+            out.update(_logical_mentioned_vars(x.select.plan))
+        elif isinstance(x, LExists):
+            out.update(_logical_mentioned_vars(x.sub))
+        for name in ("input", "left", "right"):
+            child = getattr(x, name, None)
+            if isinstance(child, LogicalOp):
+                rec(child)
+
+    rec(op)
+    return out
+
+
 # ----------------------------------------------------------- projection push
 def phys_out_vars(op: PhysicalOp) -> Set[str]:
     """Static output-variable set of a physical subtree."""
@@ -506,7 +551,8 @@ def phys_out_vars(op: PhysicalOp) -> Set[str]:
     if isinstance(op, (PHashJoin, PBindJoin, PNestedLoopJoin, PUnion, PMinus,
                        PLeftJoin)):
         return phys_out_vars(op.left) | phys_out_vars(op.right)
-    if isinstance(op, PFilter):
+    if isinstance(op, (PFilter, PExists)):
+        # variables bound only inside an EXISTS group are local to it
         return phys_out_vars(op.input)
     from .physical import PExchange
     if isinstance(op, PExchange):
@@ -580,6 +626,20 @@ def annotate_needed(op: PhysicalOp, needed):
     if isinstance(op, PFilter):
         cond_vars = set(op.condition.variables())
         annotate_needed(op.input, None if needed is None else set(needed) | cond_vars)
+        return
+    if isinstance(op, PExists):
+        # the input keeps what is needed above plus every variable the inner
+        # group shares or reads; the unit-row plan keeps the shared variables
+        # only, so with nothing shared it needs no column at all.  The
+        # probed plan keeps everything, as PMinus's probed right side does:
+        # a join's left side restricts `needed` to its own variables and
+        # would drop the incoming rows' hidden key id and correlated columns.
+        outer = phys_out_vars(op.input)
+        shared = outer & op.sub_bind_vars
+        annotate_needed(op.input, None if needed is None
+                        else set(needed) | (outer & op.sub_read_vars))
+        annotate_needed(op.sub, None)
+        annotate_needed(op.sub_free, shared)
         return
     if isinstance(op, PBind):
         from ..engine.filters import _collect_vars

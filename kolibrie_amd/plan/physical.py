@@ -119,6 +119,37 @@ class PMinus(PhysicalOp):
 
 
 @dataclass
+class PExists(PhysicalOp):
+    """`[NOT] EXISTS { group }`: appends the hidden boolean column `mark`
+    to its input rows; the PFilter above reads and drops it.
+
+    A row passes EXISTS iff the inner group, evaluated with the row's
+    bindings visible, has a solution compatible with the row (UNBOUND cells
+    are compatible with anything).  `sub` is the inner plan for rows that
+    arrive with the outer bindings (planned with them bound), `sub_free`
+    the plan for one evaluation from the unit row.  `sub_bind_vars` is
+    what the inner patterns can bind, `sub_read_vars` every variable the
+    inner group mentions; `correlated_vars` are the outer variables that
+    inner FILTER / BIND expressions read and the inner patterns do not
+    bind.  Execution modes: ExecutionEngine._exists_mask."""
+    input: PhysicalOp = field(default_factory=PUnit)
+    sub: PhysicalOp = field(default_factory=PUnit)
+    sub_free: PhysicalOp = field(default_factory=PUnit)
+    mark: str = ""
+    negated: bool = False
+    correlated_vars: tuple = ()
+    sub_bind_vars: frozenset = frozenset()
+    sub_read_vars: frozenset = frozenset()
+    est_sub_rows: float = 0.0
+
+    @property
+    def key_var(self) -> str:
+        """Hidden key-id column of the probed mode (unique per operator,
+        so nested EXISTS do not clash)."""
+        return self.mark + "\x00key"
+
+
+@dataclass
 class PConstStar(PhysicalOp):
     """Star of >=2 (CONST subject, CONST predicate, ?var) patterns: fetch
     the subject's SPO region once and evaluate every pattern host-side in
@@ -190,7 +221,7 @@ def op_certain_vars(op: PhysicalOp) -> set:
         return op_certain_vars(op.left) & op_certain_vars(op.right)
     if isinstance(op, (PLeftJoin, PMinus)):
         return op_certain_vars(op.left)
-    if isinstance(op, (PFilter, PExchange)):
+    if isinstance(op, (PFilter, PExchange, PExists)):
         return op_certain_vars(op.input)
     if isinstance(op, PBind):
         base = op_certain_vars(op.input)
@@ -229,7 +260,7 @@ def op_possible_vars(op: PhysicalOp):
         return l | r
     if isinstance(op, PMinus):
         return op_possible_vars(op.left)
-    if isinstance(op, (PFilter, PExchange)):
+    if isinstance(op, (PFilter, PExchange, PExists)):
         return op_possible_vars(op.input)
     if isinstance(op, PBind):
         base = op_possible_vars(op.input)
@@ -260,6 +291,9 @@ def plan_key(op: PhysicalOp) -> str:
         return f"{tag}[{plan_key(op.left)},{plan_key(op.right)}]"
     if isinstance(op, PExchange):
         return f"X({op.mode},{op.var})[{plan_key(op.input)}]"
+    if isinstance(op, PExists):
+        return (f"E({op.negated})[{plan_key(op.input)},"
+                f"{plan_key(op.sub)}]")
     if hasattr(op, "input"):
         return f"{type(op).__name__}[{plan_key(op.input)}]"
     return type(op).__name__
