@@ -2259,6 +2259,7 @@ chain_total_kernel(unsigned long long* __restrict__ parts,
 constexpr int kPackKeyBits = 11;
 constexpr int kPackZBits = 32 - kPackKeyBits;
 constexpr int kPackChunk = 8;
+constexpr int kDenseChunk = 16;  // key bytes per chunk of the dense format
 constexpr uint32_t kPackPadRow = kChainSpan;
 static_assert((1 << kPackKeyBits) == kChainSpan, "a key offset is 11 bits");
 static_assert(kChainPad >= 1, "the pad rows' bin lies behind the slice");
@@ -2266,14 +2267,16 @@ static_assert(kChainPad >= 1, "the pad rows' bin lies behind the slice");
 constexpr int kPackPreChunks = 2 * kChainWave;
 
 enum ChainPackStat { kPackBad = 0, kPackRows = 1, kPackZMaxInv = 2,
-                     kPackZMax = 3, kPackStats = 4 };
+                     kPackZMax = 3, kDenseBad = 4, kPackStats = 5 };
 
 // the per-tile half of the rule, the tiles' row chunks (for the offsets)
-// and the row total
+// and the row total; with key_chunks, the tiles' key chunks of the dense
+// format too
 __global__ void chain_pack_rule_kernel(
     const int32_t* __restrict__ seed_b, int64_t m, int64_t n_tiles,
     const int64_t* __restrict__ win, int k, int hp, int lds_min,
-    int64_t* __restrict__ chunks, unsigned long long* __restrict__ stats) {
+    int64_t* __restrict__ chunks, int64_t* __restrict__ key_chunks,
+    unsigned long long* __restrict__ stats) {
   for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n_tiles;
        t += (int64_t)gridDim.x * blockDim.x) {
     uint32_t first = static_cast<uint32_t>(seed_b[t * kChainTile]);
@@ -2283,6 +2286,9 @@ __global__ void chain_pack_rule_kernel(
     bool ok = last - first < static_cast<uint32_t>(kChainSpan)
         && (span == 0 || span > lds_min);
     chunks[t] = (span + kPackChunk - 1) / kPackChunk;
+    // the dense format's 16-byte chunks of one byte per key
+    if (key_chunks)
+      key_chunks[t] = ok ? (last - first) / kDenseChunk + 1 : 0;
     if (!ok) atomicOr(stats + kPackBad, 1ull);
     if (span)
       atomicAdd(stats + kPackRows, static_cast<unsigned long long>(span));
@@ -2540,6 +2546,300 @@ chain_count_packed_kernel(const uint4* __restrict__ pseeds,
     atomicAdd(parts + (blockIdx.x % n_parts) * kChainPartStride, acc);
 }
 
+// ---- dense tiles (format 2): run lengths for the keys, bit-packed z --------
+// Seeds and window rows are both sorted by key, so a tile's key column is
+// its first key plus a run length per key, and z needs only the bits of its
+// span.  Per tile t of kChainTile consecutive seeds with keys [first, last]:
+//   keys   one byte per key of first..last: low nibble = this tile's seeds
+//          with that key, high nibble = the window's rows with that key (the
+//          full count, also for a key whose seeds straddle two tiles).
+//          Padded with zero bytes to a multiple of kDenseChunk (16) bytes;
+//          lane l reads chunk l, and chunk 64 + l when the tile has more
+//          than 1024 keys.
+//   zs     z - zmin of the tile's seeds at kW bits each, kW uniform for the
+//          registration: lane l owns the seeds l, 64 + l, ... 960 + l of
+//          the tile (slot s = seed / 64) as one string of 16 * kW bits,
+//          slot s at bit s * kW, kept in kW / 2 dwords.  Of these the
+//          first 4 * (kW / 8) are stored as planes of one dwordx4 per lane,
+//          the rest as planes of one dword per lane (chain_dense_zs_at), so
+//          that every load of the wave is one contiguous stretch.  The tail
+//          tile is padded with zeros; a padding seed is never counted,
+//          because no key's low nibble covers its place.
+//   recs   per tile {first, the keys' offset in 16-byte chunks, the number
+//          of keys, 0}.
+// The kernel writes each seed's multiplicity from the further hop into LDS
+// at its place in seed order, takes the wave's prefix sum of the lanes' seed
+// nibbles, and then every lane walks its 16 keys: rows(key) times the
+// multiplicities of the key's seeds.  No histogram: no bin zeroing and no
+// LDS atomics.  Place p sits at dword p + p / 16 of the slice: when keys and
+// seeds are 1:1 the lanes' reads are 16 places apart, and the odd stride of
+// 17 dwords keeps them on different banks.
+// The rule, on top of the packed format's: a further hop that reads z; no
+// key with more than 15 of a tile's seeds; no key in a tile's range with more
+// than 15 window rows; KOLIBRIE_CHAIN_DENSE is not 0.  Anything that misses
+// only these keeps the 6-byte format.
+constexpr int kDenseRound = kDenseChunk * kChainWave;  // keys per round
+constexpr int kDenseMaxRun = 15;
+constexpr int kDenseSlotStride = kChainWave + kChainWave / 16;
+// places 0..1024 at dword p + p / 16: place 1024 (dword 1088) is what a
+// key with no seed behind the tile's last seed reads, with its rows masked
+// to 0 (chain_dense_keys), so the slice carries 16 spare dwords for it
+constexpr int kDenseLds = kChainTile + kChainTile / 16 + 16;
+// the widths the kernel is instantiated for; z spans below 2^21
+constexpr int kDenseWidths[] = {8, 16, 18, 20, 22};
+constexpr int kDenseNWidths = sizeof(kDenseWidths) / sizeof(kDenseWidths[0]);
+static_assert(kDenseWidths[kDenseNWidths - 1] > kPackZBits,
+              "every z span the packed rule admits is served");
+static_assert(kChainSpan <= 2 * kDenseRound, "two rounds cover a tile's keys");
+
+enum ChainDenseKind { kDenseDirect = 0, kDenseTable32 = 1 };
+
+// the dword of a tile's zs that holds lane `lane`'s k-th dword
+__host__ __device__ __forceinline__ int chain_dense_zs_at(int w, int lane,
+                                                          int k) {
+  int q4 = (w / 8) * 4;
+  return k < q4 ? (k / 4) * (kChainWave * 4) + lane * 4 + (k & 3)
+                : q4 * kChainWave + (k - q4) * kChainWave + lane;
+}
+
+// the per-element half of the dense rule: a run of 16 equal keys among one
+// tile's seeds, or among the region's rows for a key inside some tile's
+// range, sets stats[kDenseBad]
+__global__ void chain_dense_rule_kernel(
+    const int32_t* __restrict__ seed_b, int64_t m,
+    const int32_t* __restrict__ key32, int64_t n,
+    unsigned long long* __restrict__ stats) {
+  bool bad = false;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+       i < max(m, n); i += (int64_t)gridDim.x * blockDim.x) {
+    if (i < m && (i % kChainTile) >= kDenseMaxRun
+        && seed_b[i] == seed_b[i - kDenseMaxRun])
+      bad = true;
+    if (i < n && i >= kDenseMaxRun && key32[i] == key32[i - kDenseMaxRun]) {
+      // in a tile's range unless it falls between two tiles or past the end
+      uint32_t key = static_cast<uint32_t>(key32[i]);
+      int64_t at = lower_bound_u32(seed_b, m, key);
+      if (at < m && (at % kChainTile != 0
+                     || static_cast<uint32_t>(seed_b[at]) == key))
+        bad = true;
+    }
+  }
+  if (bad) atomicOr(stats + kDenseBad, 1ull);
+}
+
+// one block per tile (grid-stride): nibble counts, z bits and the record,
+// added into zeroed buffers.  `offs` is the inclusive prefix sum of the
+// tiles' key chunks.
+__global__ void __launch_bounds__(kBlock)
+chain_dense_tiles_kernel(const int32_t* __restrict__ seed_b,
+                         const int32_t* __restrict__ seed_z, int64_t m,
+                         int64_t n_tiles, const int32_t* __restrict__ key32,
+                         const int64_t* __restrict__ win, int k, int hp,
+                         const int64_t* __restrict__ offs, uint32_t zmin,
+                         int w, uint32_t* __restrict__ keys,
+                         uint32_t* __restrict__ zs,
+                         uint4* __restrict__ recs) {
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    uint32_t first = static_cast<uint32_t>(seed_b[t * kChainTile]);
+    uint32_t last =
+        static_cast<uint32_t>(seed_b[min((t + 1) * kChainTile, m) - 1]);
+    uint32_t nkeys = last - first + 1;
+    int64_t chunks = (nkeys + kDenseChunk - 1) / kDenseChunk;
+    int64_t off = offs[t] - chunks;
+    uint32_t* tk = keys + off * (kDenseChunk / 4);
+    uint32_t* tz = zs + t * (kChainTile / 32) * w;
+    for (int i = threadIdx.x; i < kChainTile; i += kBlock) {
+      int64_t idx = t * kChainTile + i;
+      if (idx >= m) break;
+      uint32_t kb = static_cast<uint32_t>(seed_b[idx]) - first;
+      atomicAdd(tk + kb / 4, 1u << (8 * (kb & 3)));
+      uint32_t rel = static_cast<uint32_t>(seed_z[idx]) - zmin;
+      int lane = i & (kChainWave - 1), bit = (i / kChainWave) * w;
+      int d = bit >> 5, sh = bit & 31;
+      atomicOr(tz + chain_dense_zs_at(w, lane, d), rel << sh);
+      if (sh + w > 32)
+        atomicOr(tz + chain_dense_zs_at(w, lane, d + 1), rel >> (32 - sh));
+    }
+    int64_t lo = win[(t * k + hp) * 2];
+    int64_t span = win[(t * k + hp) * 2 + 1] - lo;
+    for (int64_t r = threadIdx.x; r < span; r += kBlock) {
+      uint32_t kb = static_cast<uint32_t>(key32[lo + r]) - first;
+      atomicAdd(tk + kb / 4, 0x10u << (8 * (kb & 3)));
+    }
+    if (threadIdx.x == 0)
+      recs[t] = make_uint4(first, static_cast<uint32_t>(off), nkeys, 0u);
+  }
+}
+
+// inclusive prefix sum over the wave's 64 lanes: within rows of 16 by DPP
+// shifts, then across the rows by the two row broadcasts
+__device__ __forceinline__ uint32_t chain_wave_scan(uint32_t x) {
+  int v = static_cast<int>(x);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);  // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);  // row_shr:8
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // bcast:15
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // bcast:31
+  return static_cast<uint32_t>(v);
+}
+
+// the seeds among a lane's 16 keys
+__device__ __forceinline__ uint32_t chain_dense_seeds(const uint4& kc) {
+  uint32_t s = (kc.x & 0x0F0F0F0Fu) + (kc.y & 0x0F0F0F0Fu)
+      + (kc.z & 0x0F0F0F0Fu) + (kc.w & 0x0F0F0F0Fu);  // each byte <= 60
+  return (s * 0x01010101u) >> 24;
+}
+
+__device__ __forceinline__ uint32_t chain_dense_mul_at(const uint32_t* lds,
+                                                       uint32_t p) {
+  return lds[p + (p >> 4)];
+}
+
+// a lane's 16 keys, whose seeds start at place `start`: rows(key) times the
+// sum of its seeds' multiplicities.  The first seed of every key is read
+// without a branch: a key with no seed reads a place it does not own, up to
+// place 1024 in kDenseLds' spare dwords, which may never have been written,
+// and its rows are masked to 0; only when some lane holds a key with two seeds or
+// more does the wave go round again for the rest.
+__device__ __forceinline__ unsigned long long chain_dense_keys(
+    const uint32_t* lds, const uint4& kc, uint32_t start) {
+  const uint32_t dw[4] = {kc.x, kc.y, kc.z, kc.w};
+  unsigned long long acc = 0;
+  uint32_t p = start;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    uint32_t n4 = dw[j] & 0x0F0F0F0Fu;
+    // 0xF0 in every byte whose seed nibble is not 0
+    uint32_t bit = (n4 + 0x0F0F0F0Fu) & 0x10101010u;
+    uint32_t rows4 = dw[j] & ((bit << 4) - bit);
+    // byte b = the seeds of the dword's keys 0..b (at most 60), by shifts:
+    // a 32-bit multiply runs at a quarter of their rate
+    uint32_t upto = n4 + (n4 << 8);
+    upto += upto << 16;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      uint32_t at =
+          b == 0 ? p : p + __builtin_amdgcn_ubfe(upto, 8 * (b - 1), 8);
+      uint32_t rows = __builtin_amdgcn_ubfe(rows4, 8 * b + 4, 4);
+      acc += static_cast<unsigned long long>(rows)
+          * chain_dense_mul_at(lds, at);
+    }
+    p += upto >> 24;
+  }
+  bool more = ((kc.x | kc.y | kc.z | kc.w) & 0x0E0E0E0Eu) != 0;
+  if (__builtin_expect(__any(more), 0)) {
+    // rare, so kept small: the 16 bytes shift through x
+    uint32_t x = kc.x, y = kc.y, z = kc.z, w = kc.w;
+    p = start;
+#pragma unroll 1
+    for (int k = 0; k < kDenseChunk; ++k) {
+      uint32_t n = x & 15u, rows = (x >> 4) & 15u;
+      unsigned long long sum = 0;
+#pragma unroll 1
+      for (uint32_t i = 1; i < n; ++i) sum += chain_dense_mul_at(lds, p + i);
+      acc += rows * sum;
+      p += n;
+      x = (x >> 8) | (y << 24);
+      y = (y >> 8) | (z << 24);
+      z = (z >> 8) | (w << 24);
+      w >>= 8;
+    }
+  }
+  return acc;
+}
+
+// slot s of a lane's bit string
+template <int kW>
+__device__ __forceinline__ uint32_t chain_dense_rel(
+    const uint32_t (&d)[kW / 2], int s) {
+  const int bit = s * kW, k = bit >> 5, sh = bit & 31;
+  if (sh + kW <= 32) return __builtin_amdgcn_ubfe(d[k], sh, kW);
+  return __builtin_amdgcn_alignbit(d[k + 1 < kW / 2 ? k + 1 : k], d[k], sh)
+      & ((1u << kW) - 1u);
+}
+
+template <int kW, int kKind>
+__global__ void __launch_bounds__(kChainWave, 6)
+chain_count_dense_kernel(const uint32_t* __restrict__ zs,
+                         const uint4* __restrict__ keys,
+                         const uint4* __restrict__ recs, int64_t n_tiles,
+                         ChainPackedHt ht,
+                         unsigned long long* __restrict__ parts,
+                         int n_parts) {
+  __shared__ uint32_t lds[kDenseLds];
+  constexpr int kDw = kW / 2, kQuads = kDw / 4;
+  constexpr int kSlots = kChainTile / kChainWave;
+  const uint32_t lane = threadIdx.x;
+  uint32_t* put = lds + lane + (lane >> 4);  // slot s goes to put[s * stride]
+  const uint32_t zoff = ht.zmin - ht.dmin;   // direct: z offset -> table slot
+  unsigned long long acc = 0;
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const uint4 rec = recs[t];
+    const uint32_t nkeys = rec.z;
+    // every load of the tile, back to back
+    const uint32_t* tz = zs + t * (kChainTile / 32 * kW);
+    uint32_t d[kDw];
+#pragma unroll
+    for (int q = 0; q < kQuads; ++q) {
+      uint4 v = reinterpret_cast<const uint4*>(tz)[q * kChainWave + lane];
+      d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z;
+      d[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int k = 4 * kQuads; k < kDw; ++k)
+      d[k] = tz[k * kChainWave + lane];
+    const uint4* tk = keys + rec.y;
+    uint4 kc0 = make_uint4(0, 0, 0, 0), kc1 = kc0;
+    if (lane * kDenseChunk < nkeys) kc0 = tk[lane];
+    if (kDenseRound + lane * kDenseChunk < nkeys) kc1 = tk[kChainWave + lane];
+    // the further hop's first probe, not waited for
+    uint32_t raw[kSlots];
+#pragma unroll
+    for (int s = 0; s < kSlots; ++s) {
+      uint32_t rel = chain_dense_rel<kW>(d, s);
+      if (kKind == kDenseDirect) {
+        uint32_t off = rel + zoff;
+        raw[s] = chain_pack_tab(ht.tab, off <= ht.dlast ? off : 0u);
+      } else {
+        raw[s] = chain_pack_tab(ht.tab, h32(ht.zmin + rel) & ht.mask);
+      }
+    }
+    // where each lane's keys' seeds start
+    const uint32_t n0 = chain_dense_seeds(kc0);
+    const uint32_t upto0 = chain_wave_scan(n0);
+#pragma unroll
+    for (int s = 0; s < kSlots; ++s) {
+      uint32_t mul = raw[s];
+      if (kKind == kDenseDirect) {
+        mul = chain_dense_rel<kW>(d, s) + zoff <= ht.dlast ? mul : 0u;
+      } else if (kKind == kDenseTable32) {
+        uint32_t v = ht.zmin + chain_dense_rel<kW>(d, s);
+        uint32_t slot = h32(v) & ht.mask;
+        uint32_t e = mul;
+        while (e != kTbl32Empty && (e >> 7) != v) {
+          slot = (slot + 1) & ht.mask;
+          e = chain_pack_tab(ht.tab, slot);
+        }
+        mul = e == kTbl32Empty ? 0u : (e & 0x7Fu);
+      }
+      put[s * kDenseSlotStride] = mul;
+    }
+    chain_wave_sync();
+    acc += chain_dense_keys(lds, kc0, upto0 - n0);
+    if (nkeys > static_cast<uint32_t>(kDenseRound)) {
+      const uint32_t n1 = chain_dense_seeds(kc1);
+      const uint32_t base1 = __builtin_amdgcn_readlane(upto0, kChainWave - 1);
+      acc += chain_dense_keys(lds, kc1, base1 + chain_wave_scan(n1) - n1);
+    }
+    chain_wave_sync();  // before the next tile's multiplicities
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    acc += __shfl_down(acc, off);
+  if (threadIdx.x == 0 && acc)
+    atomicAdd(parts + (blockIdx.x % n_parts) * kChainPartStride, acc);
+}
+
 // KOLIBRIE_CHAIN_GRID caps the chain kernel's grid in place of the default
 // below (0 or unset: the default), so that a small input can be made to
 // walk several tiles per wave, and a large one to take a wave per tile.
@@ -2591,6 +2891,28 @@ inline void chain_launch(const int32_t* seed_b, const int32_t* seed_z,
     hipLaunchKernelGGL(chain_total_kernel, dim3(1), dim3(kChainParts), 0,
                        stream, parts, total, host_out);
     HIP_OK(hipGetLastError());
+  }
+}
+
+// the dense kernel's instance for a width and a kind of further hop
+using ChainDenseFn = void (*)(const uint32_t*, const uint4*, const uint4*,
+                              int64_t, ChainPackedHt, unsigned long long*,
+                              int);
+template <int kW>
+static ChainDenseFn chain_dense_fn_of(int kind) {
+  return kind == kDenseDirect ? chain_count_dense_kernel<kW, kDenseDirect>
+                              : chain_count_dense_kernel<kW, kDenseTable32>;
+}
+// one instance per entry of kDenseWidths, which is the only list of them
+template <int kI = 0>
+static ChainDenseFn chain_dense_fn(int w, int kind) {
+  if constexpr (kI == kDenseNWidths) {
+    TORCH_CHECK(false, "chain: no dense kernel for width ", w);
+    return nullptr;
+  } else {
+    if (w == kDenseWidths[kI])
+      return chain_dense_fn_of<kDenseWidths[kI]>(kind);
+    return chain_dense_fn<kI + 1>(w, kind);
   }
 }
 
@@ -2698,8 +3020,13 @@ struct ChainServe {
   // packed tiles (see chain_pack_tiles_kernel): they replace seed_b, seed_z
   // and win when the registration qualifies
   at::Tensor pseeds, prows, recs;
+  // dense tiles (see chain_count_dense_kernel): they take the packed tiles'
+  // place, with the same records tensor, when the dense rule holds too
+  at::Tensor dkeys, dzs;
+  int dense_w = 0, dense_kind = 0, dense_resident = 1;
   ChainPackedHt pht{};
-  bool packed = false;
+  bool packed = false;  // either tile format
+  bool dense = false;
   std::vector<at::Tensor> keep;
   ChainHops hops{};
   int64_t m = 0, n_tiles = 0, grid_cap = 0;
@@ -2756,24 +3083,38 @@ static void chain_try_pack(ChainServe& cs, const at::Tensor& seed_b,
       pht.mask = static_cast<uint32_t>(hops.tmask[ht]);
     }
   }
+  // the dense format is tried when the further hop reads z
+  const char* denv = getenv("KOLIBRIE_CHAIN_DENSE");
+  const bool try_dense = use_z && !(denv && atoi(denv) == 0);
   auto opts = seed_b.options().dtype(at::kLong);
   auto stats = at::zeros({kPackStats}, opts);
-  auto chunks = at::empty({cs.n_tiles}, opts);
+  auto chunks = at::empty({try_dense ? 2 : 1, cs.n_tiles}, opts);
   auto* stats_u = reinterpret_cast<unsigned long long*>(
       stats.data_ptr<int64_t>());
   hipLaunchKernelGGL(chain_pack_rule_kernel, dim3(grid_for(cs.n_tiles)),
                      dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
                      cs.m, cs.n_tiles, cs.win.data_ptr<int64_t>(), hops.k, hp,
-                     hops.lds_min, chunks.data_ptr<int64_t>(), stats_u);
+                     hops.lds_min, chunks.data_ptr<int64_t>(),
+                     try_dense ? chunks.data_ptr<int64_t>() + cs.n_tiles
+                               : nullptr,
+                     stats_u);
   HIP_OK(hipGetLastError());
+  if (try_dense) {
+    hipLaunchKernelGGL(chain_dense_rule_kernel,
+                       dim3(grid_for(std::max(cs.m, hops.n[hp]))),
+                       dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
+                       cs.m, hop_key32[hp].data_ptr<int32_t>(), hops.n[hp],
+                       stats_u);
+    HIP_OK(hipGetLastError());
+  }
   if (use_z) {
     hipLaunchKernelGGL(chain_pack_zrange_kernel, dim3(grid_for(cs.m)),
                        dim3(kBlock), 0, stream, seed_z.data_ptr<int32_t>(),
                        cs.m, stats_u);
     HIP_OK(hipGetLastError());
   }
-  auto offs = at::cumsum(chunks, 0);
-  auto host = at::cat({stats, offs.slice(0, cs.n_tiles - 1)}).cpu();
+  auto offs = at::cumsum(chunks, 1);
+  auto host = at::cat({stats, offs.select(1, cs.n_tiles - 1)}).cpu();
   const int64_t* st = host.data_ptr<int64_t>();
   const int64_t total_chunks = st[kPackStats];
   const uint32_t zmin = ~static_cast<uint32_t>(st[kPackZMaxInv]);
@@ -2783,11 +3124,42 @@ static void chain_try_pack(ChainServe& cs, const at::Tensor& seed_b,
   if (st[kPackRows] > 2 * (cs.m + hops.n[hp])) return;
   if (total_chunks > 0xFFFFFFFFll) return;
   pht.zmin = use_z ? zmin : 0u;
+  cs.recs = at::empty({cs.n_tiles * 4}, seed_b.options().dtype(at::kInt));
+  if (try_dense && st[kDenseBad] == 0
+      && st[kPackStats + 1] <= 0xFFFFFFFFll) {
+    // the narrowest instantiated width that holds zmax - zmin
+    int w = 0;
+    for (int i = kDenseNWidths - 1; i >= 0; --i)
+      if (static_cast<uint64_t>(zmax - zmin) >> kDenseWidths[i] == 0)
+        w = kDenseWidths[i];
+    cs.dense_kind =
+        pht.kind == kPackHtTable32 ? kDenseTable32 : kDenseDirect;
+    // counts and bits are added into zeroed buffers
+    cs.dkeys = at::zeros({st[kPackStats + 1] * (kDenseChunk / 4)},
+                         seed_b.options().dtype(at::kInt));
+    cs.dzs = at::zeros({cs.n_tiles * (kChainTile / 32) * w},
+                       seed_b.options().dtype(at::kInt));
+    hipLaunchKernelGGL(
+        chain_dense_tiles_kernel,
+        dim3(static_cast<int>(std::min<int64_t>(cs.n_tiles, 65536))),
+        dim3(kBlock), 0, stream, seed_b.data_ptr<int32_t>(),
+        seed_z.data_ptr<int32_t>(), cs.m, cs.n_tiles,
+        hop_key32[hp].data_ptr<int32_t>(), cs.win.data_ptr<int64_t>(), hops.k,
+        hp, offs.data_ptr<int64_t>() + cs.n_tiles, zmin, w,
+        reinterpret_cast<uint32_t*>(cs.dkeys.data_ptr<int32_t>()),
+        reinterpret_cast<uint32_t*>(cs.dzs.data_ptr<int32_t>()),
+        reinterpret_cast<uint4*>(cs.recs.data_ptr<int32_t>()));
+    HIP_OK(hipGetLastError());
+    cs.dense_w = w;
+    cs.dense_resident = chain_resident(chain_dense_fn(w, cs.dense_kind));
+    cs.pht = pht;
+    cs.packed = cs.dense = true;
+    return;
+  }
   cs.pseeds = at::empty({cs.n_tiles * kChainTile},
                         seed_b.options().dtype(at::kInt));
   cs.prows = at::empty({std::max<int64_t>(1, total_chunks) * kPackChunk},
                        seed_b.options().dtype(at::kShort));
-  cs.recs = at::empty({cs.n_tiles * 4}, seed_b.options().dtype(at::kInt));
   hipLaunchKernelGGL(
       chain_pack_tiles_kernel,
       dim3(static_cast<int>(std::min<int64_t>(cs.n_tiles, 65536))),
@@ -2873,7 +3245,22 @@ int64_t serve_chain_count(int64_t id) {
   // there (first call) or by chain_total_kernel in the previous call
   unsigned long long* total_u =
       reinterpret_cast<unsigned long long*>(total_ptr);
-  if (cs.packed) {
+  if (cs.dense) {
+    int64_t grid = std::min<int64_t>(
+        cs.n_tiles, cs.grid_cap > 0 ? cs.grid_cap : cs.dense_resident);
+    hipLaunchKernelGGL(
+        chain_dense_fn(cs.dense_w, cs.dense_kind),
+        dim3(static_cast<int>(grid)), dim3(kChainWave), 0, stream,
+        reinterpret_cast<const uint32_t*>(cs.dzs.data_ptr<int32_t>()),
+        reinterpret_cast<const uint4*>(cs.dkeys.data_ptr<int32_t>()),
+        reinterpret_cast<const uint4*>(cs.recs.data_ptr<int32_t>()),
+        cs.n_tiles, cs.pht, total_u + kChainPartStride, kChainParts);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(chain_total_kernel, dim3(1), dim3(kChainParts), 0,
+                       stream, total_u + kChainPartStride, total_u,
+                       cs.pinned_dev);
+    HIP_OK(hipGetLastError());
+  } else if (cs.packed) {
     hipLaunchKernelGGL(
         chain_count_packed_kernel,
         dim3(chain_grid(cs.n_tiles, cs.grid_cap, true)), dim3(kChainWave), 0,
@@ -2913,6 +3300,55 @@ bool chain_serve_packed(int64_t id) {
   const auto& cs = g_chain_serves.at(id);
   TORCH_CHECK(cs != nullptr, "chain serve handle ", id, " was released");
   return cs->packed;
+}
+
+// 0: the columns, 1: the 6-byte packed tiles, 2: the dense tiles
+int64_t chain_serve_format(int64_t id) {
+  const auto& cs = g_chain_serves.at(id);
+  TORCH_CHECK(cs != nullptr, "chain serve handle ", id, " was released");
+  return cs->dense ? 2 : cs->packed ? 1 : 0;
+}
+
+// A dense registration's tiles decoded on the host, for the round-trip
+// test: (seed_b, seed_z, the tiles' window row keys one tile after the
+// other), ids as non-negative int64.
+std::vector<at::Tensor> chain_serve_decode(int64_t id) {
+  const auto& csp = g_chain_serves.at(id);
+  TORCH_CHECK(csp != nullptr, "chain serve handle ", id, " was released");
+  const ChainServe& cs = *csp;
+  TORCH_CHECK(cs.dense, "chain_serve_decode: not a dense registration");
+  auto keys_t = cs.dkeys.cpu(), zs_t = cs.dzs.cpu(), recs_t = cs.recs.cpu();
+  const auto* keys = reinterpret_cast<const uint8_t*>(
+      keys_t.data_ptr<int32_t>());
+  const auto* zs = reinterpret_cast<const uint32_t*>(zs_t.data_ptr<int32_t>());
+  const auto* recs = reinterpret_cast<const uint32_t*>(
+      recs_t.data_ptr<int32_t>());
+  const int w = cs.dense_w;
+  std::vector<int64_t> sb, sz, rows;
+  for (int64_t t = 0; t < cs.n_tiles; ++t) {
+    const uint32_t first = recs[4 * t], nkeys = recs[4 * t + 2];
+    const uint8_t* tk = keys + int64_t{recs[4 * t + 1]} * kDenseChunk;
+    for (uint32_t j = 0; j < nkeys; ++j) {
+      const int64_t key = int64_t{first} + j;
+      for (int i = 0; i < (tk[j] & 15); ++i) sb.push_back(key);
+      for (int i = 0; i < (tk[j] >> 4); ++i) rows.push_back(key);
+    }
+    const uint32_t* tz = zs + t * (kChainTile / 32) * w;
+    const int64_t valid = std::min<int64_t>(kChainTile, cs.m - t * kChainTile);
+    for (int i = 0; i < valid; ++i) {
+      const int lane = i % kChainWave, bit = (i / kChainWave) * w;
+      const int d = bit >> 5, sh = bit & 31;
+      uint64_t v = tz[chain_dense_zs_at(w, lane, d)];
+      if (sh + w > 32)
+        v |= uint64_t{tz[chain_dense_zs_at(w, lane, d + 1)]} << 32;
+      sz.push_back(int64_t{cs.pht.zmin}
+                   + static_cast<int64_t>((v >> sh) & ((1u << w) - 1u)));
+    }
+  }
+  auto out = [](const std::vector<int64_t>& v) {
+    return at::tensor(v, at::kLong);
+  };
+  return {out(sb), out(sz), out(rows)};
 }
 
 void release_chain_serve(int64_t id) {
@@ -5556,6 +5992,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "one-call serving: direct launches + pinned 8-byte readback");
   m.def("chain_serve_packed", &chain_serve_packed,
         "whether a serve handle took the packed-tile format (6 B per seed)");
+  m.def("chain_serve_format", &chain_serve_format,
+        "0 = columns, 1 = 6-byte packed tiles, 2 = dense tiles",
+        py::arg("id"));
+  m.def("chain_serve_decode", &chain_serve_decode,
+        "(seed_b, seed_z, row_keys) decoded on the host from a dense "
+        "registration's tiles (for tests)", py::arg("id"));
   m.def("release_chain_serve", &release_chain_serve,
         "drop a cached serve handle (store changed)");
   m.def("build_count_table32", &build_count_table32,
