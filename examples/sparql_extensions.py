@@ -22,11 +22,19 @@ def main():
     ex:alice ex:email "alice@x" .
     ex:alice ex:worksFor ex:acme . ex:acme ex:locatedIn ex:berlin .
     ex:bob ex:worksFor ex:acme .
+    ex:alice ex:budget 10 . ex:bob ex:budget 100 . ex:carol ex:budget 1 .
+    ex:alice ex:price 5 , 50 . ex:bob ex:price 50 , 500 .
     """)
 
     print("OPTIONAL:",
           db.query(f'SELECT ?p ?m WHERE {{ ?p <{EX}knows> ?q . '
                    f'OPTIONAL {{ ?p <{EX}email> ?m }} }}'))
+    # the optional group's FILTER reads ?b from outside the group: it is the
+    # LeftJoin's condition, and a row with no offer under its budget stays
+    print("OPTIONAL + condition:",
+          sorted(db.query(f'SELECT ?x ?p WHERE {{ ?x <{EX}budget> ?b . '
+                          f'OPTIONAL {{ ?x <{EX}price> ?p . '
+                          f'FILTER(?p < ?b) }} }}')))
     print("ASK:", db.query(f'ASK {{ <{EX}alice> <{EX}knows> ?x }}'))
     print("path seq:",
           db.query(f'SELECT ?c WHERE {{ <{EX}alice> '

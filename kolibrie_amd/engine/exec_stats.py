@@ -13,6 +13,12 @@ _COUNTERS: Dict[str, int] = {
     # BFS levels that found a non-empty frontier
     "PATH_REACH_SOURCES": 0,
     "PATH_REACH_LEVELS": 0,
+    # OPTIONAL (engine/executor.py left_outer_join): evaluations per mode,
+    # and the (left, right) index pairs that were materialised
+    "OPTIONAL_NATIVE": 0,
+    "OPTIONAL_FUSED_COND": 0,
+    "OPTIONAL_GENERIC": 0,
+    "OPTIONAL_PAIRS_EMITTED": 0,
 }
 
 enabled = True

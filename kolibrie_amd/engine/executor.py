@@ -233,7 +233,8 @@ class ExecutionEngine:
             right = self.execute(op.right, Bindings.unit(self.device))
             if left.is_empty():
                 return left
-            return left_outer_join(left, right, needed)
+            return left_outer_join(left, right, needed, op.condition,
+                                   self.db)
         if isinstance(op, PMinus):
             left = self.execute(op.left, incoming)
             if left.is_empty() and not _subtree_has_exchange(op.right):
@@ -1403,27 +1404,81 @@ def _compat_nlj(left: Bindings, right: Bindings, shared: Sequence[str],
 _LOJ_ROWVAR = "\x00loj_row"  # internal row-id column (never a user var)
 
 
-def left_outer_join(left: Bindings, right: Bindings,
-                    needed=None) -> Bindings:
-    """OPTIONAL: every left row survives; matched rows extend with right
-    columns, unmatched rows pad the right-only columns UNBOUND (SPARQL
-    left outer join; engine extension beyond the reference subset).
+OPTIONAL_MODES = ("auto", "join", "probe")
 
-    Matched-ness is tracked by a hidden per-row id column carried through
-    the inner join, so a left row is padded iff it produced NO joined row —
-    correct even when the shared-variable set is empty (cartesian: every
-    left row matches whenever right is non-empty) or left shared vars are
-    UNBOUND (compat semantics), where MINUS-style anti_join would
-    disagree."""
+
+def optional_mode() -> str:
+    """KOLIBRIE_OPTIONAL_MODE, default `auto`; an unknown value raises, like
+    KOLIBRIE_EXISTS_MODE.  `join` evaluates the optional group once from the
+    unit row and left-joins it.  `probe` is reserved for evaluating the group
+    with the left rows as incoming rows, which this engine does not do yet:
+    it raises too, and `auto` means `join`."""
+    import os
+    mode = os.environ.get("KOLIBRIE_OPTIONAL_MODE") or "auto"
+    if mode not in OPTIONAL_MODES:
+        raise ValueError(f"KOLIBRIE_OPTIONAL_MODE={mode!r}: expected one of "
+                         + ", ".join(OPTIONAL_MODES))
+    if mode == "probe":
+        raise NotImplementedError(
+            "KOLIBRIE_OPTIONAL_MODE=probe: the probed right side is not "
+            "implemented; use auto or join")
+    return mode
+
+
+def left_outer_join(left: Bindings, right: Bindings, needed=None,
+                    condition=None, db=None) -> Bindings:
+    """OPTIONAL as LeftJoin(left, right, condition): every left row survives.
+    A compatible pair on which `condition` (a CompiledExpr over the merged
+    row, or None) holds extends the left row with the right columns; a left
+    row with no such pair appears once, the right-only columns UNBOUND.  The
+    surviving pairs come first, then the unmatched left rows in left order.
+    With `needed` empty only the row count, the sum of max(pairs_i, 1), is
+    computed.  One mode per evaluation, each with an exec_stats counter:
+
+      OPTIONAL_NATIVE      device rows, one to four shared variables, no
+                           UNBOUND shared cell and left.n * right.n above
+                           the broadcast-compare bound of join_bindings: the
+                           K14 left_join kernel.  OPTIONAL_FUSED_COND is
+                           bumped as well when the condition compiled to a K5
+                           program that the kernel runs on each pair; one
+                           that does not compile (a string predicate, more
+                           than 16 columns or 128 ops) filters the kernel's
+                           unconditioned pairs afterwards.
+      OPTIONAL_GENERIC     everything else: join_bindings with a hidden
+                           row-id column, which is right with no shared
+                           variable (cartesian) and with UNBOUND shared
+                           cells (compatibility), where MINUS-style
+                           anti_join would disagree.
+
+    OPTIONAL_PAIRS_EMITTED counts the (left, right) index pairs that any
+    mode materialised; the count form of the native mode leaves it alone."""
+    optional_mode()
     if right.is_empty():
         return left
     dev = left.device
+    count_only = needed is not None and len(needed) == 0
+    shared = [v for v in left.variables if v in right.cols]
+    if shared and len(shared) <= 4 and left.n * right.n > 262_144:
+        from ..ops import native_for
+        native = native_for(left.col(shared[0]))
+        if native is not None and not (
+                _any_unbound(left, shared) or _any_unbound(right, shared)):
+            return _left_join_native(native, left, right, shared, needed,
+                                     condition, db)
+    exec_stats.bump("OPTIONAL_GENERIC")
     rowid = torch.arange(left.n, dtype=torch.int32, device=dev)
     inner = join_bindings(left.with_col(_LOJ_ROWVAR, rowid), right, None)
+    if condition is not None and not inner.is_empty():
+        inner = inner.select(condition.eval_mask(inner, db))
+    exec_stats.bump("OPTIONAL_PAIRS_EMITTED", inner.n)
     if inner.is_empty():
-        return left
+        return Bindings({}, left.n, dev) if count_only else left
+    rows = inner.col(_LOJ_ROWVAR).long()
+    if count_only:
+        pairs = torch.bincount(rows, minlength=left.n)
+        return Bindings({}, int(pairs.clamp(min=1).sum().item()), dev)
     matched = torch.zeros(left.n, dtype=torch.bool, device=dev)
-    matched[inner.col(_LOJ_ROWVAR).long()] = True
+    matched[rows] = True
     inner = inner.project([v for v in inner.variables if v != _LOJ_ROWVAR])
     if needed is not None:
         inner = _prune(inner, needed)
@@ -1432,6 +1487,64 @@ def left_outer_join(left: Bindings, right: Bindings,
     unmatched = left.select(~matched)
     if needed is not None:
         unmatched = _prune(unmatched, needed)
+    return Bindings.concat([inner, unmatched], dev)
+
+
+def _any_unbound(b: Bindings, variables: Sequence[str]) -> bool:
+    """Does any of the columns hold an UNBOUND cell?  Read off the rows'
+    flag where it is clear, else checked."""
+    if not b.maybe_unbound:
+        return False
+    return any(bool((b.col(v) == UNBOUND).any().item()) for v in variables)
+
+
+def _left_join_native(native, left: Bindings, right: Bindings,
+                      shared: Sequence[str], needed, condition,
+                      db) -> Bindings:
+    """The K14 modes of left_outer_join."""
+    dev = left.device
+    count_only = needed is not None and len(needed) == 0
+    exec_stats.bump("OPTIONAL_NATIVE")
+    lk = [left.col(v).contiguous() for v in shared]
+    rk = [right.col(v).contiguous() for v in shared]
+    prog = None
+    if condition is not None:
+        from ..ops.filter_bytecode import compile_join_condition
+        prog = compile_join_condition(condition.ast, left, right,
+                                      db.value_column(),
+                                      cache_holder=condition)
+        if prog is not None:
+            exec_stats.bump("OPTIONAL_FUSED_COND")
+    if condition is None or prog is not None:
+        if count_only:
+            pairs = native.left_join_counts(lk, rk, prog)
+            return Bindings({}, int(pairs.clamp(min=1).sum().item()), dev)
+        li, ri, matched = native.left_join(lk, rk, prog)
+        matched = matched.view(torch.bool)
+        exec_stats.bump("OPTIONAL_PAIRS_EMITTED", li.numel())
+    else:
+        # the kernel joins, the evaluator of engine/filters.py judges the
+        # merged pairs; matched is what survives
+        li, ri, _ = native.left_join(lk, rk, None)
+        exec_stats.bump("OPTIONAL_PAIRS_EMITTED", li.numel())
+        if li.numel():
+            merged = _merge_pairs(left, right, li, ri, shared,
+                                  set(condition.variables()))
+            keep = condition.eval_mask(merged, db)
+            li, ri = li[keep], ri[keep]
+        if count_only:
+            pairs = torch.bincount(li, minlength=left.n)
+            return Bindings({}, int(pairs.clamp(min=1).sum().item()), dev)
+        matched = torch.zeros(left.n, dtype=torch.bool, device=dev)
+        matched[li] = True
+    if li.numel() == 0:
+        return left
+    inner = _merge_pairs(left, right, li, ri, shared, needed)
+    # a cell that either side left UNBOUND outside the key stays so
+    inner.maybe_unbound = left.maybe_unbound or right.maybe_unbound
+    if bool(matched.all().item()):
+        return inner
+    unmatched = _prune(left.select(~matched), needed)
     return Bindings.concat([inner, unmatched], dev)
 
 

@@ -99,6 +99,27 @@ class CompiledExpr:
         return out
 
 
+def format_expr(e: Expr) -> str:
+    """Surface form of an expression, for explain()."""
+    if isinstance(e, EVar):
+        return f"?{e.name}"
+    if isinstance(e, ELit):
+        return e.value
+    if isinstance(e, (ECmp, EArith)):
+        return f"({format_expr(e.left)} {e.op} {format_expr(e.right)})"
+    if isinstance(e, EAnd):
+        return f"({format_expr(e.left)} && {format_expr(e.right)})"
+    if isinstance(e, EOr):
+        return f"({format_expr(e.left)} || {format_expr(e.right)})"
+    if isinstance(e, ENot):
+        return f"!{format_expr(e.inner)}"
+    if isinstance(e, EFunc):
+        return f"{e.name}({', '.join(format_expr(a) for a in e.args)})"
+    if isinstance(e, (EExists, EExistsMark)):
+        return "EXISTS{..}"
+    return type(e).__name__
+
+
 def _children(e: Expr):
     if isinstance(e, (EAnd, EOr)):
         return (e.left, e.right)

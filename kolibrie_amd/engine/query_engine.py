@@ -23,7 +23,8 @@ class QueryEngine:
         from ..plan.lower import build_logical_plan
         from ..plan.optimizer import Streamertail, annotate_needed
         from ..plan.physical import (
-            PBind, PBindJoin, PExists, PFilter, PHashJoin, PIndexScan, PMinus,
+            PBind, PBindJoin, PExists, PFilter, PHashJoin, PIndexScan,
+            PLeftJoin, PMinus,
             PNestedLoopJoin, PStarJoin, PSubquery, PTableScan, PUnion,
             PUnit, PValues,
         )
@@ -61,6 +62,15 @@ class QueryEngine:
             elif isinstance(op, (PHashJoin, PBindJoin, PNestedLoopJoin,
                                  PUnion, PMinus)):
                 lines.append(pad + name)
+                rec(op.left, indent + 1)
+                rec(op.right, indent + 1)
+            elif isinstance(op, PLeftJoin):
+                # the join condition: the optional group's FILTER conjuncts
+                # that read a variable from outside the group
+                from .filters import format_expr
+                cond = "" if op.condition is None else \
+                    f" [condition: {format_expr(op.condition.ast)}]"
+                lines.append(f"{pad}{name}{cond}")
                 rec(op.left, indent + 1)
                 rec(op.right, indent + 1)
             elif isinstance(op, PFilter):

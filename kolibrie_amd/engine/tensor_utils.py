@@ -186,6 +186,31 @@ def merge_join_indices(
     return li, ri
 
 
+def left_join_torch(left_keys: Rows, right_keys: Rows, cond_mask_fn=None
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(li int64[t], ri int64[t], matched uint8[l]): the key-equal pairs that
+    pass `cond_mask_fn(li, ri) -> bool[pairs]` (None: all of them), grouped
+    by ascending left row, and whether left row i kept any pair.
+
+    The torch mirror of the K14 left_join kernel and the oracle of its
+    tests: group_index + merge_join_indices + a mask over the pairs.  Any
+    number of key columns; no key cell may be UNBOUND.  (The engine's own
+    path without the kernel is the generic mode of
+    executor.left_outer_join, which also handles UNBOUND and missing
+    keys.)"""
+    l = left_keys[0].numel()
+    dev = left_keys[0].device
+    gid, _ = group_index([torch.cat([a, b])
+                          for a, b in zip(left_keys, right_keys)])
+    li, ri = merge_join_indices(gid[:l], gid[l:])
+    if cond_mask_fn is not None and li.numel():
+        keep = cond_mask_fn(li, ri)
+        li, ri = li[keep], ri[keep]
+    matched = torch.zeros(l, dtype=torch.uint8, device=dev)
+    matched[li] = 1
+    return li, ri, matched
+
+
 def pack2(hi: torch.Tensor, lo: torch.Tensor) -> torch.Tensor:
     """Pack two int32 (u32-view) columns into one int64 key.
 

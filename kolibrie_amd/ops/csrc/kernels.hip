@@ -20,6 +20,9 @@
 //   K12 path_reach — property paths from a bound endpoint: multi-source
 //                    level-synchronous BFS over a CSR adjacency, 64 sources
 //                    per pass as the bits of per-node uint64 masks.
+//   K14 left_join  — OPTIONAL as LeftJoin(A, P, F): the K2 table over the
+//                    right side, the K5 program run on every key-equal pair
+//                    inside the chain walk, count + emit + matched flags.
 //
 // Design notes (per CDNA4 guide): wave64, 256-thread blocks, grid-stride
 // loops capped so the 256-CU chip is saturated without oversubscription;
@@ -540,7 +543,92 @@ struct FilterProg {
 struct BindCols {
   const int32_t* c[kMaxCols];
   int k;
+  // cell of column slot a for the row under test (K5 has one row index)
+  __device__ __forceinline__ int32_t at(int32_t a, int64_t row, int64_t) const {
+    return c[a][row];
+  }
 };
+
+// One evaluation of the program.  `cols.at(a, i, b)` reads the cell of column
+// slot a for the row i (K5) or the pair of rows (i, b) (K14) under test.
+// Forced inline and handed the kernel's column argument by reference, so each
+// kernel indexes that argument in place (a closure over it lands in scratch).
+template <typename Cols>
+__device__ __forceinline__ bool filter_vm(const FilterProg& prog,
+                                          const double* __restrict__ value_col,
+                                          int64_t value_n, const Cols& cols,
+                                          int64_t i, int64_t b) {
+  int32_t ids[kMaxStack];
+  double vals[kMaxStack];
+  // the boolean stack and the validity (NaN / div0) of each val slot are
+  // bit stacks: bit s is slot s
+  uint32_t bools = 0, ok = 0;
+  int si = 0, sv = 0, sb = 0;
+  auto push_b = [&](bool r) {
+    bools = (bools & ~(1u << sb)) | (static_cast<uint32_t>(r) << sb);
+    ++sb;
+  };
+  auto set_ok = [&](int s, bool v) {
+    ok = (ok & ~(1u << s)) | (static_cast<uint32_t>(v) << s);
+  };
+  for (int pc = 0; pc < prog.n_ops; ++pc) {
+    int32_t op = prog.ops[pc];
+    int32_t a = prog.args[pc];
+    switch (op) {
+      case OP_PUSH_ID: ids[si++] = cols.at(a, i, b); break;
+      case OP_PUSH_CONST_ID: ids[si++] = a; break;
+      case OP_PUSH_VAL: {
+        int32_t id = cols.at(a, i, b);
+        int64_t u = static_cast<uint32_t>(id);
+        double v = (u < value_n && id != kUnbound) ? value_col[u] : 0.0;
+        vals[sv] = v; set_ok(sv, id != kUnbound); ++sv;
+        break;
+      }
+      case OP_PUSH_CONST_VAL: vals[sv] = prog.consts[a]; set_ok(sv, true); ++sv; break;
+      case OP_EQ_ID: { bool r = ids[si-2] == ids[si-1] && ids[si-2] != kUnbound;
+                       si -= 2; push_b(r); break; }
+      case OP_NE_ID: { bool r = ids[si-2] != ids[si-1] && ids[si-2] != kUnbound
+                                && ids[si-1] != kUnbound;
+                       si -= 2; push_b(r); break; }
+      case OP_LT: case OP_GT: case OP_LE: case OP_GE:
+      case OP_EQ_VAL: case OP_NE_VAL: {
+        double x = vals[sv-2], y = vals[sv-1];
+        bool v = ((ok >> (sv-2)) & 3u) == 3u;
+        sv -= 2;
+        bool r = false;
+        if (op == OP_LT) r = x < y;
+        else if (op == OP_GT) r = x > y;
+        else if (op == OP_LE) r = x <= y;
+        else if (op == OP_GE) r = x >= y;
+        else if (op == OP_EQ_VAL) r = x == y;
+        else r = x != y;
+        push_b(r && v);
+        break;
+      }
+      case OP_ADD: case OP_SUB: case OP_MUL: case OP_DIV: {
+        double x = vals[sv-2], y = vals[sv-1];
+        bool v = ((ok >> (sv-2)) & 3u) == 3u;
+        sv -= 2;
+        double r = 0.0;
+        if (op == OP_ADD) r = x + y;
+        else if (op == OP_SUB) r = x - y;
+        else if (op == OP_MUL) r = x * y;
+        else { if (y == 0.0) v = false; else r = x / y; }
+        vals[sv] = r; set_ok(sv, v); ++sv;
+        break;
+      }
+      case OP_AND: { bool r = ((bools >> (sb-2)) & 3u) == 3u; sb -= 2; push_b(r); break; }
+      case OP_OR:  { bool r = ((bools >> (sb-2)) & 3u) != 0u; sb -= 2; push_b(r); break; }
+      case OP_NOT: bools ^= 1u << (sb-1); break;
+      case OP_BOUND: push_b(cols.at(a, i, b) != kUnbound); break;
+      case OP_IS_TRIPLE: { int32_t id = ids[--si];
+                           push_b((id < 0) && (id != kUnbound)); break; }
+      case OP_PUSH_TRUE: push_b(true); break;
+      case OP_PUSH_FALSE: push_b(false); break;
+    }
+  }
+  return sb > 0 ? ((bools >> (sb-1)) & 1u) != 0u : false;
+}
 
 __global__ void filter_eval(FilterProg prog, BindCols cols,
                             const double* __restrict__ value_col,
@@ -548,68 +636,125 @@ __global__ void filter_eval(FilterProg prog, BindCols cols,
                             bool* __restrict__ out) {
   for (int64_t row = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; row < n;
        row += (int64_t)gridDim.x * blockDim.x) {
-    int32_t ids[kMaxStack];
-    double vals[kMaxStack];
-    bool bools[kMaxStack];
-    bool ok[kMaxStack];   // NaN / div0 validity per val slot
-    int si = 0, sv = 0, sb = 0;
-    for (int pc = 0; pc < prog.n_ops; ++pc) {
-      int32_t op = prog.ops[pc];
-      int32_t a = prog.args[pc];
-      switch (op) {
-        case OP_PUSH_ID: ids[si++] = cols.c[a][row]; break;
-        case OP_PUSH_CONST_ID: ids[si++] = a; break;
-        case OP_PUSH_VAL: {
-          int32_t id = cols.c[a][row];
-          int64_t u = static_cast<uint32_t>(id);
-          double v = (u < value_n && id != kUnbound) ? value_col[u] : 0.0;
-          vals[sv] = v; ok[sv] = (id != kUnbound); ++sv;
-          break;
-        }
-        case OP_PUSH_CONST_VAL: vals[sv] = prog.consts[a]; ok[sv] = true; ++sv; break;
-        case OP_EQ_ID: { bool r = ids[si-2] == ids[si-1] && ids[si-2] != kUnbound;
-                         si -= 2; bools[sb++] = r; break; }
-        case OP_NE_ID: { bool r = ids[si-2] != ids[si-1] && ids[si-2] != kUnbound
-                                  && ids[si-1] != kUnbound;
-                         si -= 2; bools[sb++] = r; break; }
-        case OP_LT: case OP_GT: case OP_LE: case OP_GE:
-        case OP_EQ_VAL: case OP_NE_VAL: {
-          double x = vals[sv-2], y = vals[sv-1];
-          bool v = ok[sv-2] && ok[sv-1];
-          sv -= 2;
-          bool r = false;
-          if (op == OP_LT) r = x < y;
-          else if (op == OP_GT) r = x > y;
-          else if (op == OP_LE) r = x <= y;
-          else if (op == OP_GE) r = x >= y;
-          else if (op == OP_EQ_VAL) r = x == y;
-          else r = x != y;
-          bools[sb++] = r && v;
-          break;
-        }
-        case OP_ADD: case OP_SUB: case OP_MUL: case OP_DIV: {
-          double x = vals[sv-2], y = vals[sv-1];
-          bool v = ok[sv-2] && ok[sv-1];
-          sv -= 2;
-          double r = 0.0;
-          if (op == OP_ADD) r = x + y;
-          else if (op == OP_SUB) r = x - y;
-          else if (op == OP_MUL) r = x * y;
-          else { if (y == 0.0) v = false; else r = x / y; }
-          vals[sv] = r; ok[sv] = v; ++sv;
-          break;
-        }
-        case OP_AND: { bool r = bools[sb-2] && bools[sb-1]; sb -= 2; bools[sb++] = r; break; }
-        case OP_OR:  { bool r = bools[sb-2] || bools[sb-1]; sb -= 2; bools[sb++] = r; break; }
-        case OP_NOT: bools[sb-1] = !bools[sb-1]; break;
-        case OP_BOUND: bools[sb++] = cols.c[a][row] != kUnbound; break;
-        case OP_IS_TRIPLE: { int32_t id = ids[--si];
-                             bools[sb++] = (id < 0) && (id != kUnbound); break; }
-        case OP_PUSH_TRUE: bools[sb++] = true; break;
-        case OP_PUSH_FALSE: bools[sb++] = false; break;
+    out[row] = filter_vm(prog, value_col, value_n, cols, row, row);
+  }
+}
+
+// ----------------------------------------------------------- K14: left join
+// OPTIONAL as LeftJoin(left, right, condition): probe row i keeps the build
+// rows b with an equal key on which the K5 program holds for the PAIR (i, b),
+// and a probe row that keeps none is reported unmatched (the caller pads it).
+// The join and the condition are one walk, since padding depends on whether
+// any pair survives: a join followed by a filter has lost the rows to pad.
+// Column slot a of the program is indexed by the probe row, or by the build
+// row where bit a of `right_mask` is set.  An empty program passes every pair.
+struct PairCols {
+  const int32_t* c[kMaxCols];
+  uint32_t right_mask;
+  __device__ __forceinline__ int32_t at(int32_t a, int64_t i, int64_t b) const {
+    return c[a][(right_mask >> a) & 1u ? b : i];
+  }
+};
+
+// Count pass: survivors per probe row, and (matched != nullptr) the flag.
+__device__ __forceinline__ void lj_count_rows(
+    const KeyCols& probe, int64_t l, const KeyCols& build,
+    const int32_t* heads, const int32_t* next, uint32_t mask,
+    const FilterProg& prog, const PairCols& cols,
+    const double* __restrict__ value_col, int64_t value_n,
+    int32_t* __restrict__ cnt, uint8_t* __restrict__ matched) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < l;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & mask;
+    int32_t c = 0;
+    for (int32_t b = heads[h]; b >= 0; b = next[b]) {
+      if (!keys_equal(probe, i, build, b)) continue;
+      if (prog.n_ops == 0 || filter_vm(prog, value_col, value_n, cols, i, b))
+        ++c;
+    }
+    cnt[i] = c;
+    if (matched != nullptr) matched[i] = c > 0;
+  }
+}
+
+// Emit pass: the same walk; row i's survivors land at its exclusive offset,
+// so the pairs come out grouped by ascending probe row.
+__device__ __forceinline__ void lj_emit_rows(
+    const KeyCols& probe, int64_t l, const KeyCols& build,
+    const int32_t* heads, const int32_t* next, uint32_t mask,
+    const FilterProg& prog, const PairCols& cols,
+    const double* __restrict__ value_col, int64_t value_n,
+    const int64_t* __restrict__ offs, int64_t* __restrict__ li_out,
+    int64_t* __restrict__ ri_out) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < l;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t h = static_cast<uint32_t>(mix_hash(probe, i)) & mask;
+    int64_t base = offs[i];
+    for (int32_t b = heads[h]; b >= 0; b = next[b]) {
+      if (!keys_equal(probe, i, build, b)) continue;
+      if (prog.n_ops == 0 ||
+          filter_vm(prog, value_col, value_n, cols, i, b)) {
+        li_out[base] = i;
+        ri_out[base] = b;
+        ++base;
       }
     }
-    out[row] = sb > 0 ? bools[sb-1] : false;
+  }
+}
+
+// hj_lds_build on the kernel argument itself: that one takes KeyCols by value,
+// and the copy, indexed in a loop, lives in scratch.
+__device__ __forceinline__ void lj_lds_build(const KeyCols& build, int64_t r,
+                                             int32_t* heads, int32_t* next) {
+  for (int j = threadIdx.x; j < kHjLdsSlots; j += blockDim.x) heads[j] = -1;
+  __syncthreads();
+  for (int64_t i = threadIdx.x; i < r; i += blockDim.x) {
+    uint32_t h = static_cast<uint32_t>(mix_hash(build, i)) & (kHjLdsSlots - 1);
+    next[i] = atomicExch(&heads[h], static_cast<int32_t>(i));
+  }
+  __syncthreads();
+}
+
+// kLds as in hj_count / hj_emit: the table over the build (right) side is
+// staged per block in LDS, or it is the global one that hj_build filled.
+template <bool kLds>
+__global__ void lj_count(KeyCols probe, int64_t l, KeyCols build, int64_t r,
+                         const int32_t* __restrict__ heads,
+                         const int32_t* __restrict__ next, uint32_t mask,
+                         FilterProg prog, PairCols cols,
+                         const double* __restrict__ value_col,
+                         int64_t value_n, int32_t* __restrict__ cnt,
+                         uint8_t* __restrict__ matched) {
+  if constexpr (kLds) {
+    __shared__ int32_t lds_heads[kHjLdsSlots];
+    __shared__ int32_t lds_next[kHjLdsRows];
+    lj_lds_build(build, r, lds_heads, lds_next);
+    lj_count_rows(probe, l, build, lds_heads, lds_next, kHjLdsSlots - 1, prog,
+                  cols, value_col, value_n, cnt, matched);
+  } else {
+    lj_count_rows(probe, l, build, heads, next, mask, prog, cols, value_col,
+                  value_n, cnt, matched);
+  }
+}
+
+template <bool kLds>
+__global__ void lj_emit(KeyCols probe, int64_t l, KeyCols build, int64_t r,
+                        const int32_t* __restrict__ heads,
+                        const int32_t* __restrict__ next, uint32_t mask,
+                        FilterProg prog, PairCols cols,
+                        const double* __restrict__ value_col, int64_t value_n,
+                        const int64_t* __restrict__ offs,
+                        int64_t* __restrict__ li_out,
+                        int64_t* __restrict__ ri_out) {
+  if constexpr (kLds) {
+    __shared__ int32_t lds_heads[kHjLdsSlots];
+    __shared__ int32_t lds_next[kHjLdsRows];
+    lj_lds_build(build, r, lds_heads, lds_next);
+    lj_emit_rows(probe, l, build, lds_heads, lds_next, kHjLdsSlots - 1, prog,
+                 cols, value_col, value_n, offs, li_out, ri_out);
+  } else {
+    lj_emit_rows(probe, l, build, heads, next, mask, prog, cols, value_col,
+                 value_n, offs, li_out, ri_out);
   }
 }
 
@@ -3765,6 +3910,154 @@ at::Tensor filter_bytecode(at::Tensor ops, at::Tensor args, at::Tensor consts,
   return out;
 }
 
+// The condition of a K14 join, validated.  `cond` is None (every key match
+// survives) or (ops, args, consts, value_col, cols, sides): a K5 program
+// whose column slot j is indexed by the left row where sides[j] == 0 and by
+// the right row where it is 1.  The tensors stay referenced by the caller's
+// tuple for the length of the call.
+struct LjCond {
+  FilterProg prog{};
+  PairCols cols{};
+  const double* value_col = nullptr;
+  int64_t value_n = 0;
+};
+
+static LjCond lj_cond(const py::object& cond, const HjSides& s,
+                      const at::Tensor& key0) {
+  LjCond out;
+  if (cond.is_none()) return out;
+  auto t = cond.cast<py::tuple>();
+  TORCH_CHECK(t.size() == 6, "left_join: cond is (ops, args, consts, "
+                             "value_col, cols, sides)");
+  auto ops = t[0].cast<at::Tensor>();
+  auto args = t[1].cast<at::Tensor>();
+  auto consts = t[2].cast<at::Tensor>();
+  auto value_col = t[3].cast<at::Tensor>();
+  auto cols = t[4].cast<std::vector<at::Tensor>>();
+  auto sides = t[5].cast<std::vector<int64_t>>();
+  TORCH_CHECK(ops.is_cuda() && args.is_cuda() && consts.is_cuda() &&
+                  value_col.is_cuda(),
+              "left_join: the program must be on the device");
+  TORCH_CHECK(ops.device() == key0.device() &&
+                  args.device() == key0.device() &&
+                  consts.device() == key0.device() &&
+                  value_col.device() == key0.device(),
+              "left_join: program and keys on different devices");
+  TORCH_CHECK(ops.dtype() == at::kInt && args.dtype() == at::kInt &&
+                  consts.dtype() == at::kDouble &&
+                  value_col.dtype() == at::kDouble,
+              "left_join: program dtypes are int32, int32, float64, float64");
+  TORCH_CHECK(ops.is_contiguous() && args.is_contiguous() &&
+                  consts.is_contiguous() && value_col.is_contiguous() &&
+                  ops.dim() == 1 && args.dim() == 1,
+              "left_join: program tensors must be contiguous 1-D");
+  TORCH_CHECK(ops.numel() == args.numel() && ops.numel() <= 128,
+              "left_join: at most 128 ops, one arg each");
+  TORCH_CHECK(cols.size() <= static_cast<size_t>(kMaxCols) &&
+                  cols.size() == sides.size(),
+              "left_join: at most 16 columns, one side flag each");
+  for (size_t j = 0; j < cols.size(); ++j) {
+    TORCH_CHECK(sides[j] == 0 || sides[j] == 1, "left_join: side is 0 or 1");
+    TORCH_CHECK(cols[j].is_cuda() && cols[j].dtype() == at::kInt &&
+                    cols[j].dim() == 1 && cols[j].is_contiguous() &&
+                    cols[j].device() == key0.device(),
+                "left_join: condition columns must be contiguous int32 on "
+                "the keys' device");
+    TORCH_CHECK(cols[j].numel() == (sides[j] ? s.r : s.l),
+                "left_join: a condition column differs in length from its "
+                "side");
+    out.cols.c[j] = cols[j].data_ptr<int32_t>();
+    if (sides[j]) out.cols.right_mask |= 1u << j;
+  }
+  out.prog.ops = ops.data_ptr<int32_t>();
+  out.prog.args = args.data_ptr<int32_t>();
+  out.prog.consts = consts.data_ptr<double>();
+  out.prog.n_ops = static_cast<int>(ops.numel());
+  out.value_col = value_col.data_ptr<double>();
+  out.value_n = value_col.numel();
+  return out;
+}
+
+static HjSides lj_sides(const std::vector<at::Tensor>& left_keys,
+                        const std::vector<at::Tensor>& right_keys) {
+  HjSides s = hj_sides(left_keys, right_keys);
+  for (size_t j = 0; j < left_keys.size(); ++j) {
+    TORCH_CHECK(left_keys[j].dim() == 1 && right_keys[j].dim() == 1 &&
+                    left_keys[j].is_contiguous() &&
+                    right_keys[j].is_contiguous(),
+                "left_join: key columns must be contiguous 1-D");
+    TORCH_CHECK(left_keys[j].numel() == s.l && right_keys[j].numel() == s.r,
+                "left_join: key columns of one side differ in length");
+    TORCH_CHECK(left_keys[j].device() == left_keys[0].device() &&
+                    right_keys[j].device() == left_keys[0].device(),
+                "left_join: key columns on different devices");
+  }
+  return s;
+}
+
+// survivors per left row (and the matched flags); both sides non-empty
+static at::Tensor lj_counts(const HjSides& s, const HjTable& t,
+                            const LjCond& c, uint8_t* matched,
+                            const at::TensorOptions& opts_int,
+                            hipStream_t stream) {
+  auto cnt = at::empty({s.l}, opts_int);
+  hipLaunchKernelGGL(t.lds ? lj_count<true> : lj_count<false>,
+                     dim3(grid_for(s.l)), dim3(kBlock), 0, stream, s.probe,
+                     s.l, s.build, s.r, t.heads.data_ptr<int32_t>(),
+                     t.next.data_ptr<int32_t>(), t.mask, c.prog, c.cols,
+                     c.value_col, c.value_n, cnt.data_ptr<int32_t>(), matched);
+  HIP_OK(hipGetLastError());
+  return cnt;
+}
+
+// K14, count-only: int32[l] pairs of left row i that pass the condition.
+at::Tensor left_join_counts(std::vector<at::Tensor> left_keys,
+                            std::vector<at::Tensor> right_keys,
+                            py::object cond) {
+  HjSides s = lj_sides(left_keys, right_keys);
+  auto opts_int = left_keys[0].options();
+  LjCond c = lj_cond(cond, s, left_keys[0]);
+  if (s.l == 0 || s.r == 0) return at::zeros({s.l}, opts_int);
+  auto stream = cur_stream();
+  return lj_counts(s, hj_table(s, opts_int, stream), c, nullptr, opts_int,
+                   stream);
+}
+
+// K14 left join: (li int64[t], ri int64[t], matched uint8[l]).  The pairs
+// are grouped by ascending li; the caller guarantees that no key cell is
+// UNBOUND.
+py::tuple left_join(std::vector<at::Tensor> left_keys,
+                    std::vector<at::Tensor> right_keys, py::object cond) {
+  HjSides s = lj_sides(left_keys, right_keys);
+  auto opts_int = left_keys[0].options();
+  auto opts_long = opts_int.dtype(at::kLong);
+  auto opts_u8 = opts_int.dtype(at::kByte);
+  LjCond c = lj_cond(cond, s, left_keys[0]);
+  if (s.l == 0 || s.r == 0) {
+    return py::make_tuple(at::empty({0}, opts_long), at::empty({0}, opts_long),
+                          at::zeros({s.l}, opts_u8));
+  }
+  auto stream = cur_stream();
+  HjTable t = hj_table(s, opts_int, stream);
+  auto matched = at::empty({s.l}, opts_u8);
+  auto cnt = lj_counts(s, t, c, matched.data_ptr<uint8_t>(), opts_int, stream);
+  auto offs = at::cumsum(cnt, 0, at::kLong);
+  int64_t total = offs[-1].item<int64_t>();
+  auto offs_excl = offs - cnt.to(at::kLong);
+  auto li = at::empty({total}, opts_long);
+  auto ri = at::empty({total}, opts_long);
+  if (total > 0) {
+    hipLaunchKernelGGL(t.lds ? lj_emit<true> : lj_emit<false>,
+                       dim3(grid_for(s.l)), dim3(kBlock), 0, stream, s.probe,
+                       s.l, s.build, s.r, t.heads.data_ptr<int32_t>(),
+                       t.next.data_ptr<int32_t>(), t.mask, c.prog, c.cols,
+                       c.value_col, c.value_n, offs_excl.data_ptr<int64_t>(),
+                       li.data_ptr<int64_t>(), ri.data_ptr<int64_t>());
+    HIP_OK(hipGetLastError());
+  }
+  return py::make_tuple(li, ri, matched);
+}
+
 // K9 string predicate -> (uint8 mask of 0/1/2, int32[1] overflow count).
 // `needle` is the pattern zero-padded to 256 bytes on the device, `m` its
 // real length.  With fold != NONE the caller passes an ASCII needle already
@@ -6018,6 +6311,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("build_cols"), py::arg("anti"), py::arg("lds_tier") = -1,
         "K13 semi join -> uint8 per probe row: has an equal build row, "
         "flipped by anti");
+  m.def("left_join", &left_join, py::arg("left_keys"), py::arg("right_keys"),
+        py::arg("cond") = py::none(),
+        "K14 conditional left outer join -> (li, ri, matched)");
+  m.def("left_join_counts", &left_join_counts, py::arg("left_keys"),
+        py::arg("right_keys"), py::arg("cond") = py::none(),
+        "K14 count-only: pairs per left row that pass the condition");
   m.def("filter_bytecode", &filter_bytecode,
         "K5 filter bytecode evaluation -> bool mask");
   m.def("str_match", &str_match,

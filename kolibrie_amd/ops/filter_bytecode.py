@@ -169,6 +169,83 @@ def _vars_of(e: Expr) -> List[str]:
     return out
 
 
+_MAX_STACK = 16   # kMaxStack in kernels.hip
+
+
+def _fits_stacks(ops: List[int]) -> bool:
+    """Does the program stay within the VM's id, value and boolean stacks?"""
+    si = sv = sb = 0
+    for op in ops:
+        if op in (OP_PUSH_ID, OP_PUSH_CONST_ID):
+            si += 1
+        elif op in (OP_PUSH_VAL, OP_PUSH_CONST_VAL):
+            sv += 1
+        elif op in (OP_EQ_ID, OP_NE_ID):
+            si -= 2
+            sb += 1
+        elif op in (OP_LT, OP_GT, OP_LE, OP_GE, OP_EQ_VAL, OP_NE_VAL):
+            sv -= 2
+            sb += 1
+        elif op in (OP_ADD, OP_SUB, OP_MUL, OP_DIV):
+            sv -= 1
+        elif op in (OP_AND, OP_OR):
+            sb -= 1
+        elif op == OP_IS_TRIPLE:
+            si -= 1
+            sb += 1
+        elif op in (OP_BOUND, OP_PUSH_TRUE, OP_PUSH_FALSE):
+            sb += 1
+        if max(si, sv, sb) > _MAX_STACK:
+            return False
+    return True
+
+
+def compile_join_condition(ast: Expr, left, right, value_col,
+                           cache_holder=None) -> Optional[Tuple]:
+    """The K14 form of a LeftJoin condition over the pair (left row, right
+    row): (ops, args, consts, value_col, cols, sides), or None when the
+    expression has no bytecode form (the caller then filters the merged
+    pairs).  Column slot j is indexed by the left row where sides[j] == 0 and
+    by the right row where it is 1; a variable on both sides is a join key,
+    equal in both, and reads the left column.  Programs are cached on
+    `cache_holder` like compile_filter's, under keys that cannot collide
+    with them."""
+    used = _vars_of(ast)
+    present = tuple((v, 0 if left.has(v) else 1) for v in used
+                    if left.has(v) or right.has(v))
+    dev = left.device
+    cache = None
+    key = ("join", present, dev)
+    if cache_holder is not None:
+        cache = getattr(cache_holder, "_fb_cache", None)
+        if cache is None:
+            cache = cache_holder._fb_cache = {}
+    hit = cache.get(key) if cache is not None else None
+    if hit is False:
+        return None
+    if hit is None:
+        hit = False
+        if len(present) <= 16:
+            c = _Compiler({v: i for i, (v, _s) in enumerate(present)})
+            try:
+                c.push_bool(ast)
+                if len(c.ops) <= 128 and _fits_stacks(c.ops):
+                    hit = (torch.tensor(c.ops, dtype=torch.int32, device=dev),
+                           torch.tensor(c.args, dtype=torch.int32, device=dev),
+                           torch.tensor(c.consts or [0.0],
+                                        dtype=torch.float64, device=dev))
+            except BytecodeError:
+                pass
+        if cache is not None:
+            cache[key] = hit
+        if hit is False:
+            return None
+    ops_t, args_t, consts_t = hit
+    cols = [(left if s == 0 else right).col(v).contiguous()
+            for v, s in present]
+    return ops_t, args_t, consts_t, value_col, cols, [s for _v, s in present]
+
+
 def compile_filter(ast: Expr, bindings, cache_holder=None) -> Optional[Tuple]:
     """Compile to (ops, args, consts, col_list) device tensors.
 

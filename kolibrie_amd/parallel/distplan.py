@@ -209,6 +209,9 @@ class DistPlanner:
             else:
                 # right side must see the GLOBAL right solutions
                 r, rp = self._bcast(r, rp)
+            # the node is rewired in place, so a PLeftJoin keeps its
+            # condition: every rank evaluates it on its own pairs, which see
+            # the same right rows as a single rank would
             op.left, op.right = l, r
             return op, lp
         if isinstance(op, PExists):

@@ -91,9 +91,14 @@ class LMinus(LogicalOp):
 
 @dataclass
 class LLeftJoin(LogicalOp):
-    """OPTIONAL left outer join."""
+    """OPTIONAL: LeftJoin(left, right, condition).  `condition` holds the
+    conjuncts of the optional group's FILTERs that read a variable the group
+    itself does not certainly bind (plan/lower.py); it is evaluated on the
+    merged row, and a left row none of whose pairs passes it is kept once,
+    unextended."""
     left: LogicalOp = field(default_factory=LUnit)
     right: LogicalOp = field(default_factory=LUnit)
+    condition: Optional[object] = None   # CompiledExpr (engine/filters.py)
 
 
 @dataclass

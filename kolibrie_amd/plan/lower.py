@@ -202,8 +202,127 @@ def build_logical_plan(
         )
     if isinstance(g, GOptional):
         from .logical import LLeftJoin
+        # A OPTIONAL { P FILTER(F) } is LeftJoin(A, P, F): F sees A's
+        # variables.  The group's own FILTERs wrap the top of g.right
+        # (parse_group); their conjuncts that P alone can answer stay there,
+        # where they cut the right side before the join, and the others
+        # become the join condition.
+        inner = g.right
+        peeled: List[Expr] = []
+        while isinstance(inner, GFilter):
+            peeled.append(inner.expr)
+            inner = inner.inner
+        certain = certain_vars(inner)
+        cond: List[Expr] = []
+        for expr in reversed(peeled):       # innermost first: source order
+            for c in _conjuncts(expr):
+                if _has_exists(c) or set(_expr_vars(c)) <= certain:
+                    inner = GFilter(c, inner)
+                else:
+                    cond.append(c)
+        condition = None
+        if cond:
+            expr = cond[0]
+            for c in cond[1:]:
+                expr = EAnd(expr, c)
+            condition = CompiledExpr(expr, db, prefixes)
         return LLeftJoin(
             build_logical_plan(g.left, db, prefixes, scope),
-            build_logical_plan(g.right, db, prefixes, scope),
+            build_logical_plan(inner, db, prefixes, scope),
+            condition,
         )
     raise ValueError(f"cannot lower {type(g).__name__}")
+
+
+def _conjuncts(e: Expr) -> List[Expr]:
+    if isinstance(e, EAnd):
+        return _conjuncts(e.left) + _conjuncts(e.right)
+    return [e]
+
+
+def _has_exists(e: Expr) -> bool:
+    if isinstance(e, EExists):
+        return True
+    if isinstance(e, (EAnd, EOr, ECmp, EArith)):
+        return _has_exists(e.left) or _has_exists(e.right)
+    if isinstance(e, ENot):
+        return _has_exists(e.inner)
+    if isinstance(e, EFunc):
+        return any(_has_exists(a) for a in e.args)
+    return False
+
+
+def _expr_vars(e: Expr) -> List[str]:
+    from ..engine.filters import _collect_vars
+    out: List[str] = []
+    _collect_vars(e, out)
+    return out
+
+
+def certain_vars(g: GGP) -> set:
+    """Variables that every solution of the group binds.  Conservative and
+    syntactic: a subset of the true set.  Triple patterns reached through
+    BGPs, joins and GRAPH (with the graph variable) count, as do BIND targets
+    whose expression cannot produce UNBOUND and VALUES columns without UNDEF;
+    a UNION gives what both branches give; the right side of OPTIONAL and
+    MINUS and a subquery give nothing."""
+    if isinstance(g, GBgp):
+        out = set()
+        for pat in g.patterns:
+            for t in (pat.s, pat.p, pat.o):
+                out.update(_term_vars(t))
+        return out
+    if isinstance(g, GJoin):
+        return certain_vars(g.left) | certain_vars(g.right)
+    if isinstance(g, GUnion):
+        return certain_vars(g.left) & certain_vars(g.right)
+    if isinstance(g, GGraph):
+        out = certain_vars(g.inner)
+        out.update(_term_vars(g.graph))
+        return out
+    if isinstance(g, (GFilter, GWindowBlock)):
+        return certain_vars(g.inner)
+    if isinstance(g, GBind):
+        out = certain_vars(g.inner)
+        # SUBJECT/PREDICATE/OBJECT of a non-triple give UNBOUND (see
+        # CompiledBind.may_produce_unbound), and so does an unbound operand
+        if not _may_be_unbound(g.expr) and set(_expr_vars(g.expr)) <= out:
+            out.add(g.var)
+        return out
+    if isinstance(g, GValues):
+        out = certain_vars(g.inner)
+        if g.rows:
+            for j, v in enumerate(g.variables):
+                if all(r[j] is not None for r in g.rows):
+                    out.add(v)
+        return out
+    if isinstance(g, (GOptional, GMinus)):
+        return certain_vars(g.left)
+    if isinstance(g, GSubQuery):
+        return certain_vars(g.inner)
+    return set()
+
+
+def _may_be_unbound(e: Expr) -> bool:
+    if isinstance(e, EFunc):
+        return (e.name in ("SUBJECT", "PREDICATE", "OBJECT")
+                or any(_may_be_unbound(a) for a in e.args))
+    if isinstance(e, (EAnd, EOr, ECmp, EArith)):
+        return _may_be_unbound(e.left) or _may_be_unbound(e.right)
+    if isinstance(e, ENot):
+        return _may_be_unbound(e.inner)
+    return False
+
+
+def _term_vars(t: str) -> List[str]:
+    """Variable names in a surface term (a quoted triple nests terms)."""
+    t = t.strip()
+    if t.startswith("?") or t.startswith("$"):
+        return [t[1:]]
+    if t.startswith("<<") and t.endswith(">>"):
+        from ..storage.database import split_quoted_triple_content
+        out: List[str] = []
+        for part in split_quoted_triple_content(t[2:-2].strip()):
+            out.extend(_term_vars(part))
+        return out
+    return []

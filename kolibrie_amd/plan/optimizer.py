@@ -163,7 +163,8 @@ class Streamertail:
         if isinstance(op, LLeftJoin):
             lp, lr, lc = self._plan(op.left, bound)
             rp, rr, rc = self._plan(op.right, bound)
-            return PLeftJoin(lp, rp), max(lr, lr * 1.0), lc + rc + lr + rr
+            return (PLeftJoin(lp, rp, op.condition), max(lr, lr * 1.0),
+                    lc + rc + lr + rr)
         if isinstance(op, LProjection):
             ip, ir, ic = self._plan(op.input, bound)
             return PProjection(list(op.variables), ip), ir, ic
@@ -508,6 +509,8 @@ def _logical_mentioned_vars(op: LogicalOp) -> Set[str]:
     def rec(x):
         if isinstance(x, LSelection):
             out.update(x.condition.variables())
+        elif isinstance(x, LLeftJoin) and x.condition is not None:
+            out.update(x.condition.variables())
         elif isinstance(x, LBind):
             from ..engine.filters import _collect_vars
             vs: List[str] = []
@@ -614,6 +617,11 @@ def annotate_needed(op: PhysicalOp, needed):
         lv = phys_out_vars(op.left)
         rv = phys_out_vars(op.right)
         shared = lv & rv
+        # the condition reads the merged row: its variables survive below
+        # the join on both sides and leave the output unless needed above
+        # (the executor prunes to op.needed)
+        if op.condition is not None:
+            shared = shared | set(op.condition.variables())
         annotate_needed(op.left,
                         None if needed is None else (set(needed) | shared) & lv)
         annotate_needed(op.right,

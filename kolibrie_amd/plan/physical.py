@@ -161,9 +161,13 @@ class PConstStar(PhysicalOp):
 
 @dataclass
 class PLeftJoin(PhysicalOp):
-    """OPTIONAL: inner join plus unmatched left rows padded UNBOUND."""
+    """OPTIONAL: inner join plus unmatched left rows padded UNBOUND.  With a
+    `condition` (a CompiledExpr over the merged row) a pair counts only when
+    it passes, and a left row with no passing pair is padded.  Execution
+    modes: engine/executor.py left_outer_join."""
     left: PhysicalOp = field(default_factory=PUnit)
     right: PhysicalOp = field(default_factory=PUnit)
+    condition: Optional[object] = None
 
 
 @dataclass
